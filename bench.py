@@ -2,8 +2,13 @@
 """bench.py -- kNN queries/sec on the FLAT path (BASELINE.json configs[1]):
 FLAT index, 10M x 768 fp32 COSINE, k=10, batch=256 queries per step.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run builds the index, warms up, times the K steps and prints the line.  --full adds everything beside the
+headline (kernel-timing region, two batches in flight, single-query scan, CPU baseline + parity, the HNSW / configs[3] /
+configs[4] legs, single-query serving, the gather A/B of N > 1).  --dump-outputs DIR writes the last timed step's answer
+(distances.npy, labels.npy, counts.npy) for comparing two builds output for output.
 
 One process per GPU.  The index (fixed total size) is sharded by contiguous row ranges over
 the N ranks ("strong" scaling: total work fixed); a step = every rank scans its shard for
@@ -463,6 +468,16 @@ def _shard_filter_ms(ix, before, after=None):
     return best, n
 
 
+def dump_outputs(dirname, dists, labels, counts):
+    """--dump-outputs: the answer of the timed path's last step as the caller of vk_index_search_batch_device receives it --
+    distances [B][k] (f32 as returned), labels [B][k] (u64 ids as f64: exact below 2^53) and the filled counts [B] (as f64)"""
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "distances.npy", np.ascontiguousarray(dists, dtype=np.float32))
+    np.save(d / "labels.npy", np.asarray(labels).view(np.uint64).astype(np.float64))
+    np.save(d / "counts.npy", np.asarray(counts).astype(np.float64))
+
+
 def _timed_steps(step, steps, warmup):
     """HIP events on the current stream + the wall clock around `steps` calls (after `warmup` untimed ones)"""
     for _ in range(warmup):
@@ -575,27 +590,31 @@ def lib_multi_gpu(args, world, rank, dist, device):
         ix, A, Q, od, ol, tabs = state["ix"], state["A"], state["Q"], state["od"], state["ol"], state["tabs"]
         st1 = ix.stats()
         dev_ms = e0.elapsed_time(e1) / args.steps
-        # per-shard kernel times: a second region of K steps with the library's event pairs around each shard's main pass
-        # (option kernel-timing: the timed region above runs without those stream markers)
-        ix.set_option("kernel-timing", 1)
-        for _ in range(2):
-            state["step"]()
-        torch.cuda.synchronize()
-        sh0 = _shard_filter_ms(ix, None)
-        for _ in range(args.steps):
-            state["step"]()
-        torch.cuda.synchronize()
-        sh1 = [ix.shard_stats(s_i) for s_i in range(ix.shard_count())]
-        ix.set_option("kernel-timing", 0)
-        per_shard_ms = [round((a.filter_kernel_ns - b.filter_kernel_ns) / 1e6 / (a.filter_batches - b.filter_batches), 4)
-                        if a.filter_batches != b.filter_batches else None for b, a in zip(sh0, sh1)]
-        res_d, res_l = od.cpu().numpy(), ol.cpu().numpy().view(np.uint64)
+        res_d, res_l, res_n = od.cpu().numpy(), ol.cpu().numpy().view(np.uint64), state["on"].cpu().numpy()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, res_d, res_l, res_n)
+        per_shard_ms = None
+        if args.full:
+            # per-shard kernel times: a second region of K steps with the library's event pairs around each shard's main pass
+            # (option kernel-timing: the timed region above runs without those stream markers)
+            ix.set_option("kernel-timing", 1)
+            for _ in range(2):
+                state["step"]()
+            torch.cuda.synchronize()
+            sh0 = _shard_filter_ms(ix, None)
+            for _ in range(args.steps):
+                state["step"]()
+            torch.cuda.synchronize()
+            sh1 = [ix.shard_stats(s_i) for s_i in range(ix.shard_count())]
+            ix.set_option("kernel-timing", 0)
+            per_shard_ms = [round((a.filter_kernel_ns - b.filter_kernel_ns) / 1e6 / (a.filter_batches - b.filter_batches), 4)
+                            if a.filter_batches != b.filter_batches else None for b, a in zip(sh0, sh1)]
         n_local = N // world
         stride = ((D + 63) // 64) * 64 * esz
         scan_bytes = n_local * stride                  # algorithmic bytes of one pass over ONE GPU's shard
         # the dominant kernel per shard: the candidate filter; its duration = the SLOWEST shard's HIP events (the library
         # records them around the launches on each shard's stream; vk_index_stats of a sharded index reports the maximum)
-        timed = [m for m in per_shard_ms if m]
+        timed = [m for m in per_shard_ms or [] if m]
         filt_ms, filt_n = (max(timed), args.steps) if timed else (None, 0)
         fan_calls = st1.fanout_calls - st0.fanout_calls
         fan_us = (st1.fanout_enqueue_ns - st0.fanout_enqueue_ns) / 1e3 / fan_calls if fan_calls else None
@@ -645,7 +664,7 @@ def lib_multi_gpu(args, world, rank, dist, device):
                                 "(distances f32, labels u64) of [lists_per_rank][batch][k] per step in one group call"}
             finally:
                 ix.set_option("shard-gather", 0)
-        gather = leg(gather_ab)
+        gather = leg(gather_ab) if args.full else None
 
         # ---- CPU baseline (same oracle leg as N = 1) + parity of the merged answer on the queries it scanned ----
         cpu = parity = None
@@ -1220,7 +1239,18 @@ def main():
                     help="test aid: every rank uses cuda:0 (with --backend gloo, two ranks can exercise the sharded path on one GPU)")
     ap.add_argument("--verify-merge", action="store_true",
                     help="test aid (N > 1, small --rows): rank 0 also builds the unsharded index and checks the merged answer against it")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline too: the kernel-timing region, two batches in flight, the single-query "
+                         "scan, the CPU baseline and its parity check, the HNSW / configs[3] / configs[4] legs, single-query serving, "
+                         "the gather A/B of N > 1 (the options of those legs take effect only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run does what its headline needs: set up, warm up, time the steps (and dump their answer), print the line
+        args.no_cpu_baseline = args.no_serving = True
+        args.single_query_steps = args.two_in_flight_steps = args.hnsw_rows = args.hybrid_rows = args.bf16_rows = 0
+        args.hnsw_sharded = False
 
     procs = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -1343,11 +1373,16 @@ def main():
     dev_ms = ev0.elapsed_time(ev1) / args.steps      # HIP events on the work stream around the K timed steps
     st_after = ix.stats()
     filt_n = st_after.filter_batches - st_before.filter_batches     # batches of the timed region that went through the candidate filter
+    # the answer of the last timed step, on the host before anything else runs on the index
+    result_d = (fin_d if world > 1 else out_d).cpu().numpy()
+    result_l = (fin_l if world > 1 else out_l).cpu().numpy().view(np.uint64)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, result_d, result_l, (fin_n if world > 1 else out_n).cpu().numpy())
     # The dominant kernel ALONE (the filter's main pass): a second region of K steps behind the timed one, with the library's
     # event pairs around that launch switched on (option kernel-timing: an event record is a marker the stream executes,
     # about 6 us of idle device each, so the timed region runs without them and `roofline.frac` is the whole step's).
     filt_ms, filt_timed = None, 0
-    if filt_n:
+    if filt_n and args.full:
         ix.set_option("kernel-timing", 1)
         for _ in range(2):
             step()
@@ -1420,13 +1455,11 @@ def main():
     # survivors of the candidate filter per query, and queries handed to the exact pass (one host-path call: the
     # device-buffer entry point reports no statistics)
     filt_stats = None
-    if filt_n and world == 1:
+    if filt_n and world == 1 and args.full:
         ix.search_batch(Q.cpu().numpy(), K)
         st_f = ix.stats()
         filt_stats = {"survivors_per_query": round(st_f.last_filter_candidates / B, 1), "reranked_per_query": round(st_f.last_filter_reranked / B, 1),
                       "queries_handed_over": int(st_f.last_filter_fallback)}
-    result_d = (fin_d if world > 1 else out_d).cpu().numpy()
-    result_l = (fin_l if world > 1 else out_l).cpu().numpy().view(np.uint64)
 
     # ---- CPU baseline + parity spot check on rank 0 (oracle = checker, never the product) ----
     cpu = None
@@ -1584,14 +1617,15 @@ def main():
                           "traffic_unit": "HBM bytes per step (early + main pass launches)", "traffic_source": traffic_src,
                           "algorithmic_bytes": scan_bytes, "priced": "whole step", "step_ms_on_stream": round(dev_ms, 4),
                           "rows_in_step": n_local,
-                          "dominant_kernel": {"kernel": filter_name, "achieved": round(kern_bytes / (filt_ms * 1e-3) / 1e9, 2),
+                          "dominant_kernel": ({"kernel": filter_name, "achieved": round(kern_bytes / (filt_ms * 1e-3) / 1e9, 2),
                                               "frac": round(kern_bytes / (filt_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
                                               "per_launch_ms": round(filt_ms, 4), "launches_timed": int(filt_timed),
                                               "rows_in_launch": main_rows, "algorithmic_bytes": kern_bytes, "traffic": kern_traffic,
                                               "measured": "the library's HIP event pairs around this launch on its stream (option "
                                                           "kernel-timing), K steps behind the timed region",
                                               "f16_mfma_tflops": round(flops / (filt_ms * 1e-3) / 1e12, 1),
-                                              "f16_mfma_frac_of_2500": round(flops / (filt_ms * 1e-3) / 1e12 / 2500.0, 4)},
+                                              "f16_mfma_frac_of_2500": round(flops / (filt_ms * 1e-3) / 1e12 / 2500.0, 4)}
+                                             if filt_ms else None),     # (its region runs with --full)
                           "early_pass": ({"kernel": filter_name.replace("flat_filter_bdma_kernel", "flat_filter_early_kernel")
                                                                .replace("flat_filter_bfmma_dma_kernel", "flat_filter_early_bfmma_dma_kernel"),
                                           "rows": n_local - main_rows,

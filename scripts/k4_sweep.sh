@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 for cfg in ${1:-0:0 0:1 2:1}; do
   M=${cfg%%:*}; W=${cfg##*:}
   echo "== VK_GEMM_MODE=$M VK_GEMM_LOCKSTEP=$W"
-  VK_GEMM_MODE=$M VK_GEMM_LOCKSTEP=$W timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --single-query-steps 0 --hnsw-rows 0 2>&1 | grep -v amdgpu.ids | tail -1 | python -c "
+  VK_GEMM_MODE=$M VK_GEMM_LOCKSTEP=$W timeout 600 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --single-query-steps 0 --hnsw-rows 0 2>&1 | grep -v amdgpu.ids | tail -1 | python -c "
 import sys, json
 for l in sys.stdin:
     try:

@@ -11,7 +11,7 @@ for cfg in ${1:-0:0 2:1}; do
   D=$ROOT/gpurun_out/pmc_m${M}_w${W}
   rm -rf $D
   VK_GEMM_MODE=$M VK_GEMM_LOCKSTEP=$W timeout 420 rocprofv3 --pmc FETCH_SIZE -d $D --output-format csv -- \
-    python $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --single-query-steps 1 --hnsw-rows 0 > $D.log 2>&1
+    python $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --single-query-steps 1 --hnsw-rows 0 > $D.log 2>&1
   echo "== mode $M lockstep $W (rc $?)"
   python $ROOT/scripts/pmc_agg.py $D | tee $ROOT/gpurun_out/pmc_m${M}_w${W}.json
   rm -rf $D

@@ -6,18 +6,19 @@
 #           the same 16 B / lane loads; carries the gfx950 1/2 factor)
 #   pass 2  TCC_HIT_sum / TCC_MISS_sum: the L2's own hit rate
 #   pass 3  whatever memory-side counters the tool lists for DRAM / MALL (printed; summed if collectable)
-# Usage: scripts/pmc_hnsw_traffic.sh ROWS NQ EF   (GPU box)  -> gpurun_out/r06_pmc_hnsw_traffic.json + .log
+# Usage: scripts/pmc_hnsw_traffic.sh ROWS NQ EF   (GPU box)  -> $OUTDIR/r06_pmc_hnsw_traffic.json + .log
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+OUTDIR=${OUTDIR:-$ROOT/bench_out}
 ROWS=${1:-10000000}; NQ=${2:-8192}; EF=${3:-128}
-OUT=$ROOT/gpurun_out/r06_pmc_hnsw_traffic
-mkdir -p $ROOT/gpurun_out
+OUT=$OUTDIR/r06_pmc_hnsw_traffic
+mkdir -p $OUTDIR
 cd /tmp && export TMPDIR=/tmp
 : > $OUT.log
 rocprofv3 -L 2>/dev/null | grep -oE "\b(TCC_[A-Z0-9_]*(DRAM|MALL|EA0_RDREQ|EA_RDREQ)[A-Z0-9_]*|FETCH_SIZE|MALL[A-Z0-9_]*)\b" | sort -u | tr '\n' ' ' > $OUT.counters
 echo "memory-side counters listed by the tool: $(cat $OUT.counters)" >> $OUT.log
 i=0
 for CNT in "FETCH_SIZE" "TCC_HIT_sum TCC_MISS_sum" "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_DRAM_sum"; do
-  i=$((i+1)); D=$ROOT/gpurun_out/pmc_hnsw_t$i; rm -rf $D
+  i=$((i+1)); D=$OUTDIR/pmc_hnsw_t$i; rm -rf $D
   timeout -s KILL 900 rocprofv3 --pmc $CNT --kernel-include-regex "hnsw_search|flat_scan_kernel<1," -d $D --output-format csv -- \
     python $ROOT/scripts/hnsw_probe.py --rows $ROWS --nq $NQ --ef $EF --calibrate > $D.log 2>&1
   echo "pass $i ($CNT) rc $?" >> $OUT.log; grep -E "^ef=|calibration" $D.log >> $OUT.log

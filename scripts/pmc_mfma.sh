@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 for DT in f32 bf16; do
   for CNT in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES" "SQ_INSTS_VALU_MFMA_MOPS_F16 SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_INSTS_MFMA SQ_WAIT_INST_ANY"; do
     Dd=$ROOT/gpurun_out/pmc_mfma_$DT; rm -rf $Dd
-    timeout 300 rocprofv3 --pmc $CNT --kernel-trace -d $Dd --output-format csv -- python $ROOT/bench.py --dtype $DT --steps 2 --warmup 1 --no-cpu-baseline --single-query-steps 0 --hnsw-rows 0 --hybrid-rows 0 --bf16-rows 0 > $Dd.log 2>&1
+    timeout 300 rocprofv3 --pmc $CNT --kernel-trace -d $Dd --output-format csv -- python $ROOT/bench.py --full --dtype $DT --steps 2 --warmup 1 --no-cpu-baseline --single-query-steps 0 --hnsw-rows 0 --hybrid-rows 0 --bf16-rows 0 > $Dd.log 2>&1
     python $ROOT/scripts/pmc_agg.py $Dd | python -c "
 import json,sys
 j=json.load(sys.stdin)

@@ -3,16 +3,17 @@
 # run, no tracing, as the guide prescribes), aggregated per kernel, calibrated on the single-query scan kernel (which
 # reads each row byte exactly once) and stamped with the hash of the kernel sources it was taken with.
 # bench.py prints `roofline.traffic` from the resulting file ONLY while that hash equals the current sources'.
-#   scripts/pmc_traffic.sh [out.json]        (run on the GPU box; default out: gpurun_out/r06_pmc_fetch_size.json)
+#   scripts/pmc_traffic.sh [out.json]        (run on the GPU box; default out: $OUTDIR/r06_pmc_fetch_size.json)
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
-OUT=${1:-$ROOT/gpurun_out/r06_pmc_fetch_size.json}
+OUTDIR=${OUTDIR:-$ROOT/bench_out}
+OUT=${1:-$OUTDIR/r06_pmc_fetch_size.json}
 case "$OUT" in /*) ;; *) OUT="$PWD/$OUT" ;; esac
-mkdir -p $ROOT/gpurun_out
+mkdir -p $OUTDIR
 cd /tmp && export TMPDIR=/tmp
-D=$ROOT/gpurun_out/pmc_traffic
+D=$OUTDIR/pmc_traffic
 rm -rf $D
 timeout 900 rocprofv3 --pmc FETCH_SIZE -d $D --output-format csv -- \
-  python $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --single-query-steps 2 --hnsw-rows 0 --hybrid-rows 0 --bf16-rows 0 > $D.log 2>&1
+  python $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --single-query-steps 2 --hnsw-rows 0 --hybrid-rows 0 --bf16-rows 0 > $D.log 2>&1
 echo "rocprofv3 rc $?"
 python $ROOT/scripts/pmc_agg.py $D > $D.agg.json
 python - "$D.agg.json" "$OUT" <<'PY'

@@ -1,15 +1,16 @@
 #!/bin/bash
 # Where a batched FLAT step's time goes, launch by launch: rocprofv3 --kernel-trace of bench.py's FLAT leg, then for the LAST
 # step of the timed region every kernel with its start offset, duration and the idle gap in front of it.
-#   scripts/step_trace.sh <tag> [bench args, e.g. --rows 1250000]   -> gpurun_out/<tag>_step_trace.log
+#   scripts/step_trace.sh <tag> [bench args, e.g. --rows 1250000]   -> $OUTDIR/<tag>_step_trace.log
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+OUTDIR=${OUTDIR:-$ROOT/bench_out}
 TAG=${1:-step}; shift
-mkdir -p $ROOT/gpurun_out
+mkdir -p $OUTDIR
 cd /tmp && export TMPDIR=/tmp
-D=$ROOT/gpurun_out/trace_$TAG
+D=$OUTDIR/trace_$TAG
 rm -rf $D
-timeout -s KILL 420 rocprofv3 --kernel-trace -d $D --output-format csv -- python $ROOT/bench.py --no-cpu-baseline --hnsw-rows 0 --hybrid-rows 0 --bf16-rows 0 --single-query-steps 0 --no-serving --steps 10 --warmup 3 "$@" > $ROOT/gpurun_out/${TAG}_bench.log 2>&1
-python - $D <<'PY' | tee $ROOT/gpurun_out/${TAG}_step_trace.log
+timeout -s KILL 420 rocprofv3 --kernel-trace -d $D --output-format csv -- python $ROOT/bench.py --full --no-cpu-baseline --hnsw-rows 0 --hybrid-rows 0 --bf16-rows 0 --single-query-steps 0 --no-serving --steps 10 --warmup 3 "$@" > $OUTDIR/${TAG}_bench.log 2>&1
+python - $D <<'PY' | tee $OUTDIR/${TAG}_step_trace.log
 import csv, glob, sys
 rows = []
 for f in glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True):
@@ -42,5 +43,5 @@ if len(steps) >= 25:
     print("a step of the second region (kernel-timing on: an event record in front of and behind the main pass):")
     show(*steps[-3])
 PY
-tail -c 600 $ROOT/gpurun_out/${TAG}_bench.log
+tail -c 600 $OUTDIR/${TAG}_bench.log
 rm -rf $D

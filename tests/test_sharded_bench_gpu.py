@@ -15,7 +15,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
-SIZES = ["--rows", "600000", "--steps", "3", "--warmup", "1", "--same-device", "--verify-merge", "--hnsw-rows", "40000",
+SIZES = ["--full", "--rows", "600000", "--steps", "3", "--warmup", "1", "--same-device", "--verify-merge", "--hnsw-rows", "40000",
          "--hybrid-rows", "20000", "--bf16-rows", "300000", "--single-query-steps", "0", "--hnsw-queries", "512", "--hybrid-queries", "512"]
 
 
@@ -61,7 +61,7 @@ def test_single_process_two_shards():
 def test_two_ranks_two_shards(mode, port):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", port, str(ROOT / "bench.py"), "--multi-gpu", mode, "--gpus", "2", "--rows", "300000", "--steps", "2",
+           "127.0.0.1", "--master-port", port, str(ROOT / "bench.py"), "--full", "--multi-gpu", mode, "--gpus", "2", "--rows", "300000", "--steps", "2",
            "--warmup", "1", "--backend", "gloo", "--same-device", "--verify-merge", "--hnsw-rows", "40000", "--hybrid-rows", "0",
            "--bf16-rows", "0", "--no-cpu-baseline", "--no-hnsw-single-ref", "--single-query-steps", "0", "--hnsw-queries", "512"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
