@@ -368,6 +368,34 @@ int vk_filter_combine(vk_index *ix, const vk_filter *a, const vk_filter *b, uint
  * and one wait per device instead of n (n <= 65535; all or nothing: on an error no out[i] is set). */
 int vk_filter_combine_batch(vk_index *ix, const vk_filter *const *a, const vk_filter *const *b, const uint32_t *ops, uint64_t n,
                             vk_filter **out);
+/* A NEW filter from an older one plus a small delta of labels, on the device.  The tag index mutates per key
+ * (src/indexes/tag.cc AddRecord / ModifyRecord / RemoveRecord: one key starts or stops matching a tag), and the schema goes
+ * from writing back to reading every few milliseconds (src/index_schema.cc:285-292): the filter of `@tag:{x}` after a write
+ * phase is the filter before it with a handful of bits changed -- and a longer label range when keys were added.  Instead of
+ * vk_filter_create over the whole posting list again (8 B per matching id over PCIe per phase) the old bitmap is copied
+ * device to device and only the changed labels travel.
+ *   result = a copy of `base` (NULL = the empty set), extended with zero bits up to `nbits`, then the clear_labels cleared,
+ *   THEN the set_labels set: a label in both lists ends up set.  Duplicates within a list are fine; labels >= nbits are
+ *   ignored, like vk_filter_create's.  vk_filter_info's allowed count of the result is exact (the device counts the bits
+ *   that really changed).
+ *   nbits below the base's -> VK_ERR_INVALID (a filter never shrinks: labels count up); a base of another index, a NULL
+ *   list with a non-zero length, n > 65535 (the limit of vk_filter_combine_batch) -> VK_ERR_INVALID; n == 0 -> VK_OK,
+ *   nothing done.  Argument errors are reported before any device work.  All or nothing: on any error no out[i] is set and
+ *   no reference is left behind.
+ *   The base is untouched (filters are immutable) and may be released before, during or after the result is used; the
+ *   same base may appear in several items of one batch.  A sharded index keeps one copy of a filter per device: every copy
+ *   gets the delta.  Per device the whole batch costs one upload of the label records, at most three launches and one wait,
+ *   however many items it has.  filters_built goes up by n. */
+typedef struct vk_filter_delta {
+  const vk_filter *base;          /* NULL = start from the empty set */
+  uint64_t nbits;                 /* label range of the result; >= the base's nbits */
+  const uint64_t *clear_labels;
+  uint64_t n_clear;
+  const uint64_t *set_labels;
+  uint64_t n_set;
+} vk_filter_delta;
+int vk_filter_apply_delta(vk_index *ix, const vk_filter_delta *item, vk_filter **out);
+int vk_filter_apply_delta_batch(vk_index *ix, const vk_filter_delta *items, uint64_t n, vk_filter **out);
 void vk_filter_retain(vk_filter *f);
 void vk_filter_release(vk_filter *f);
 /* nbits, and the number of allowed labels (counted on the device: what query::UsePreFiltering, planner.cc:21-45, wants as

@@ -249,11 +249,38 @@ class VectorGpu : public VectorBase {
   // ---- the write -> read phase switch (src/index_schema.cc:285-292): staged mutations are published to the device (single
   // AddRecord calls of the phase are linked in bulk, on the device when there are thousands) and filters cached before it
   // are no longer served
+  // ... except the filters of MAINTAINED predicates (below), which are carried over the switch: the filter of the phase before
+  // plus the changes noted during the write phase, derived on the device in one vk_filter_apply_delta_batch
   absl::Status OnWritePhaseEnd() {
-    filter_epoch_.fetch_add(1, std::memory_order_relaxed);
-    return VkToStatus(vk_index_flush(ix_));
+    const uint64_t previous = filter_epoch_.fetch_add(1, std::memory_order_relaxed);
+    const int rc = vk_index_flush(ix_);
+    if (maintained_count_.load(std::memory_order_acquire) != 0) CarryMaintainedFilters(previous, previous + 1);
+    return VkToStatus(rc);
   }
   uint64_t FilterEpoch() const { return filter_epoch_.load(std::memory_order_relaxed); }
+
+  // ---- maintained predicates ------------------------------------------------------------------------------------------
+  // A cache key (e.g. "@tag:{x}") whose filter the module keeps current instead of rebuilding it from the posting list after
+  // every write phase (8 B per matching key over PCIe and a hash lookup per key, every 11 ms under write traffic).  The tag
+  // index knows, at the moment it mutates (src/indexes/tag.cc AddRecord / ModifyRecord / RemoveRecord), which record starts
+  // or stops matching which tag: it says so with NoteFilterChange, from any writer thread.  OnWritePhaseEnd() applies the
+  // notes of the phase (the last note per id wins) to the filter cached under the previous epoch and stores the result under
+  // the new one: the first query after the switch is a cache hit.  A key without a cached filter (never built, or evicted)
+  // drops its notes -- the next BuildFilter rebuilds it from the fetchers, as for a key that is not maintained.
+  void MaintainFilter(absl::string_view cache_key) {
+    std::lock_guard<std::mutex> l(maintained_mu_);
+    if (maintained_.emplace(std::string(cache_key), std::vector<FilterNote>{}).second) maintained_count_.fetch_add(1, std::memory_order_release);
+  }
+  void ForgetFilter(absl::string_view cache_key) {
+    std::lock_guard<std::mutex> l(maintained_mu_);
+    if (maintained_.erase(std::string(cache_key))) maintained_count_.fetch_sub(1, std::memory_order_release);
+  }
+  void NoteFilterChange(absl::string_view cache_key, uint64_t internal_id, bool matches) {
+    if (maintained_count_.load(std::memory_order_acquire) == 0) return;
+    std::lock_guard<std::mutex> l(maintained_mu_);
+    auto it = maintained_.find(std::string(cache_key));
+    if (it != maintained_.end()) it->second.push_back(FilterNote{internal_id, matches});   // (a key that is not maintained: dropped)
+  }
 
   // ---- filters --------------------------------------------------------------------------------------------------------
   // From the EntriesFetchers of the predicate (what DoSearchVector has in hand before it calls PerformVectorSearch,
@@ -489,7 +516,16 @@ class VectorGpu : public VectorBase {
       return VkToStatus(rc);
     }
   }
-  absl::Status RemoveRecordImpl(uint64_t internal_id) override { return VkToStatus(vk_index_remove(ix_, internal_id)); }
+  // (a record that leaves the vector index matches no predicate any more: every maintained filter loses its bit, so that
+  //  allowed() -- the planner's estimate -- stays exact)
+  absl::Status RemoveRecordImpl(uint64_t internal_id) override {
+    const int rc = vk_index_remove(ix_, internal_id);
+    if (rc == VK_OK && maintained_count_.load(std::memory_order_acquire) != 0) {
+      std::lock_guard<std::mutex> l(maintained_mu_);
+      for (auto &kv : maintained_) kv.second.push_back(FilterNote{internal_id, false});
+    }
+    return VkToStatus(rc);
+  }
   // same label again = in-place update (vector_flat.cc:178-193 pokes data_; vector_hnsw.cc:273-286 markDelete + addPoint)
   absl::Status ModifyRecordImpl(uint64_t internal_id, absl::string_view record) override { return AddRecordImpl(internal_id, record); }
 
@@ -595,6 +631,55 @@ class VectorGpu : public VectorBase {
     if (!cache_key.empty()) (void)vk_index_filter_cache_put(ix_, cache_key.data(), cache_key.size(), epoch, f);
     return ref;
   }
+
+  // OnWritePhaseEnd for the maintained keys: one derivation batch for all of them.  A failure never leaves a stale filter
+  // under the new epoch: the notes are gone and the key is simply not stored again (the next query rebuilds it).
+  struct FilterNote { uint64_t id; bool matches; };
+  void CarryMaintainedFilters(uint64_t previous_epoch, uint64_t epoch) {
+    std::vector<std::pair<std::string, std::vector<FilterNote>>> keys;
+    {
+      std::lock_guard<std::mutex> l(maintained_mu_);
+      keys.reserve(maintained_.size());
+      for (auto &kv : maintained_) {
+        keys.emplace_back(kv.first, std::vector<FilterNote>{});
+        keys.back().second.swap(kv.second);
+      }
+    }
+    const uint64_t nbits = GetMaxInternalLabel() + 1;
+    struct Pending { const std::string *key; VkFilterRef base; std::vector<uint64_t> set, clear; };
+    std::vector<Pending> pending;
+    for (auto &kn : keys) {
+      vk_filter *hit = nullptr;
+      if (vk_index_filter_cache_get(ix_, kn.first.data(), kn.first.size(), previous_epoch, &hit) != VK_OK || !hit) continue;
+      VkFilterRef base = VkFilterRef::Adopt(hit);
+      uint64_t base_nbits = 0;
+      (void)vk_filter_info(hit, &base_nbits, nullptr);
+      if (kn.second.empty() && base_nbits == nbits) {   // nothing changed: the same handle under the new epoch, no copy
+        (void)vk_index_filter_cache_put(ix_, kn.first.data(), kn.first.size(), epoch, hit);
+        continue;
+      }
+      if (base_nbits > nbits) continue;                 // (a filter never shrinks: rebuilt by the next query)
+      std::unordered_map<uint64_t, bool> last;          // the last note per id wins
+      for (const FilterNote &n : kn.second) last[n.id] = n.matches;
+      Pending p{&kn.first, std::move(base), {}, {}};
+      for (const auto &kv : last) (kv.second ? p.set : p.clear).push_back(kv.first);
+      pending.push_back(std::move(p));
+    }
+    if (pending.empty()) return;
+    std::vector<vk_filter_delta> items(pending.size());
+    std::vector<vk_filter *> out(pending.size(), nullptr);
+    for (size_t i = 0; i < pending.size(); ++i)
+      items[i] = vk_filter_delta{pending[i].base.get(), nbits, pending[i].clear.data(), pending[i].clear.size(), pending[i].set.data(),
+                                 pending[i].set.size()};
+    if (vk_filter_apply_delta_batch(ix_, items.data(), items.size(), out.data()) != VK_OK) return;
+    for (size_t i = 0; i < pending.size(); ++i) {
+      (void)vk_index_filter_cache_put(ix_, pending[i].key->data(), pending[i].key->size(), epoch, out[i]);
+      vk_filter_release(out[i]);
+    }
+  }
+  std::mutex maintained_mu_;
+  std::unordered_map<std::string, std::vector<FilterNote>> maintained_;   // cache key -> the notes of the current write phase, in order
+  std::atomic<size_t> maintained_count_{0};
 
   // one asynchronous search: lives from SearchAsync to its completion callback
   struct AsyncSearch {

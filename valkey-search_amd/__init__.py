@@ -62,6 +62,12 @@ class Stats(C.Structure):
                 ("last_filter_final_rows", C.c_uint64)]
 
 
+class FilterDelta(C.Structure):
+    """vk_filter_delta"""
+    _fields_ = [("base", C.c_void_p), ("nbits", C.c_uint64), ("clear_labels", C.c_void_p), ("n_clear", C.c_uint64),
+                ("set_labels", C.c_void_p), ("n_set", C.c_uint64)]
+
+
 WRITE_CHUNK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)
 READ_CHUNK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64))
 SEARCH_DONE = C.CFUNCTYPE(None, C.c_void_p, C.c_int)
@@ -142,6 +148,8 @@ def lib() -> C.CDLL:
     L.vk_filter_create.argtypes = [vp, u64, vp, u64, vp, u64, vp, C.POINTER(vp)]
     L.vk_filter_combine.argtypes = [vp, vp, vp, u32, C.POINTER(vp)]
     L.vk_filter_combine_batch.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u32), u64, C.POINTER(vp)]
+    L.vk_filter_apply_delta.argtypes = [vp, C.POINTER(FilterDelta), C.POINTER(vp)]
+    L.vk_filter_apply_delta_batch.argtypes = [vp, C.POINTER(FilterDelta), u64, C.POINTER(vp)]
     L.vk_filter_retain.argtypes = [vp]
     L.vk_filter_retain.restype = None
     L.vk_filter_release.argtypes = [vp]
@@ -302,6 +310,29 @@ class Index:
         O = (C.c_uint32 * n)(*[code[p[2] if len(p) > 2 else op] for p in pairs])
         out = (C.c_void_p * n)()
         _check(lib().vk_filter_combine_batch(self._h, A, B, O, n, out))
+        return [Filter(C.c_void_p(out[i])) for i in range(n)]
+
+    def filter_apply_delta(self, base, nbits, set=None, clear=None) -> Filter:
+        """vk_filter_apply_delta: a NEW filter = base (None = empty) grown to nbits, `clear` cleared, then `set` set"""
+        return self.filter_apply_delta_batch([(base, nbits, set, clear)], _single=True)[0]
+
+    def filter_apply_delta_batch(self, items, _single=False):
+        """vk_filter_apply_delta_batch: [(base, nbits, set, clear), ...] -> one Filter each; per device one upload, at most
+        three launches and one wait for the whole batch"""
+        n = len(items)
+        tab = (FilterDelta * max(n, 1))()
+        keep = []
+        for i, (base, nbits, st, cl) in enumerate(items):
+            st = None if st is None else np.ascontiguousarray(st, dtype=np.uint64)
+            cl = None if cl is None else np.ascontiguousarray(cl, dtype=np.uint64)
+            keep += [st, cl]
+            tab[i] = FilterDelta(None if base is None else base._h, int(nbits), _ptr(cl), 0 if cl is None else cl.size,
+                                 _ptr(st), 0 if st is None else st.size)
+        out = (C.c_void_p * max(n, 1))()
+        if _single:
+            _check(lib().vk_filter_apply_delta(self._h, tab, out))
+        else:
+            _check(lib().vk_filter_apply_delta_batch(self._h, tab, n, out))
         return [Filter(C.c_void_p(out[i])) for i in range(n)]
 
     def filter_cache_get(self, key: bytes, epoch: int):

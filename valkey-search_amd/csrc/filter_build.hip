@@ -123,6 +123,66 @@ __global__ __launch_bounds__(kThreads) void filter_combine_batch_kernel(const Co
   }
 }
 
+// ---- a NEW filter from an old one plus a delta of labels (vk_filter_apply_delta[_batch]) ---------------------------------------
+// The tag index changes a few keys per write phase (src/indexes/tag.cc AddRecord / ModifyRecord / RemoveRecord); the filter of
+// `@tag:{x}` after the phase is the filter before it with those few bits flipped, and perhaps a longer label range.  A batch
+// of n derivations is: ONE copy-and-grow launch (blockIdx.y = item), then the label records of ALL items in one launch for
+// the clears and one for the sets (stream order gives "cleared, then set": a label in both lists ends up set).
+struct DeltaItem {
+  unsigned long long *dst;
+  const unsigned long long *base;   // nullptr: start empty
+  unsigned long long base_words, dst_words, nbits, unused;
+};
+static_assert(sizeof(DeltaItem) == kFilterDeltaItemWords * 8, "the host fills the table as plain words");
+
+// dst[0 .. dst_words) = base's words, zeros behind them, the last word masked to nbits; the slack word behind the bitmap cleared
+// (the block may be a recycled one, and every reader of whole words relies on it)
+__global__ __launch_bounds__(kThreads) void filter_delta_copy_kernel(const DeltaItem *items) {
+  const DeltaItem it = items[blockIdx.y];
+  const unsigned long long tail = it.nbits & 63u ? ~0ull >> (64 - (it.nbits & 63u)) : ~0ull;
+  for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < it.dst_words; i += (uint64_t)gridDim.x * kThreads) {
+    unsigned long long v = i < it.base_words ? it.base[i] : 0ull;
+    if (i + 1 == it.dst_words) v &= tail;
+    it.dst[i] = v;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) it.dst[it.dst_words] = 0;
+}
+
+// One record per label: bits 0-39 the label, bits 40-55 the item it belongs to (kFilterDeltaLabelBits).  One 64-bit atomic
+// AND-NOT (kSet = false) or OR (kSet = true) per record; the atomic returns the word as it was, so exactly one of the lanes
+// that name a bit sees it change, duplicates included, and counts[item] moves by -1 / +1 for that lane alone: the result's
+// population is the base's plus counts[item] (two's complement), with no popcount pass.  Records of one item lie together, so
+// a wave usually holds one item: its lanes' changes are summed in registers and leave as one atomic add.
+template <bool kSet>
+__global__ __launch_bounds__(kThreads) void filter_delta_apply_kernel(const DeltaItem *items, const uint64_t *recs, uint64_t n,
+                                                                       unsigned long long *counts) {
+  const uint32_t lane = threadIdx.x & 63u;
+  // (the loop bound is the wave's first record: every lane of a wave makes the same number of trips, as the shuffles need)
+  for (uint64_t i0 = (uint64_t)blockIdx.x * kThreads + (threadIdx.x & ~63u); i0 < n; i0 += (uint64_t)gridDim.x * kThreads) {
+    const uint64_t i = i0 + lane;
+    uint32_t item = ~0u;
+    unsigned long long d = 0;
+    if (i < n) {
+      const uint64_t rec = recs[i];
+      item = (uint32_t)(rec >> kFilterDeltaLabelBits);
+      const uint64_t label = rec & (((uint64_t)1 << kFilterDeltaLabelBits) - 1);
+      if (label < items[item].nbits) {   // (labels beyond the bitmap are ignored, like vk_filter_create's)
+        unsigned long long *w = items[item].dst + (label >> 6);
+        const unsigned long long m = 1ull << (label & 63);
+        if (kSet) d = (atomicOr(w, m) & m) == 0 ? 1ull : 0ull;
+        else d = (atomicAnd(w, ~m) & m) != 0 ? ~0ull : 0ull;   // (-1)
+      }
+    }
+    const uint32_t first = (uint32_t)__shfl((int)item, 0, 64);   // (lane 0's record exists: i0 < n)
+    if (__all(i >= n || item == first)) {
+      for (int off = 32; off; off >>= 1) d += __shfl_down(d, off, 64);
+      if (lane == 0 && d) atomicAdd(&counts[first], d);
+    } else if (d) {
+      atomicAdd(&counts[item], d);
+    }
+  }
+}
+
 inline uint32_t grid_for(uint64_t items) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, (items + kThreads - 1) / kThreads), 256 * 8); }
 }  // namespace
 
@@ -158,6 +218,26 @@ hipError_t launch_filter_combine_batch(const uint64_t *d_items, uint32_t n, uint
   if (n > 65535) return hipErrorInvalidValue;
   const uint32_t gx = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, (words + kThreads * 4 - 1) / (kThreads * 4)), 64);
   hipLaunchKernelGGL(filter_combine_batch_kernel, dim3(gx, n), dim3(kThreads), 0, s, reinterpret_cast<const CombineItem *>(d_items), words, d_counts);
+  return hipGetLastError();
+}
+
+// d_items: [n][kFilterDeltaItemWords] words = {dst, base or 0, base_words, dst_words, nbits, 0} (device pointers)
+hipError_t launch_filter_delta_copy(const uint64_t *d_items, uint32_t n, uint64_t max_dst_words, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  if (n > 65535) return hipErrorInvalidValue;
+  // (a lone item gets the whole grid of a memory-bound pass, a large batch a few blocks per item: about 2048 blocks in all)
+  const uint32_t gx = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, (max_dst_words + kThreads - 1) / kThreads), std::max<uint32_t>(8, 2048 / n));
+  hipLaunchKernelGGL(filter_delta_copy_kernel, dim3(gx, n), dim3(kThreads), 0, s, reinterpret_cast<const DeltaItem *>(d_items));
+  return hipGetLastError();
+}
+// d_recs: [n_recs] records (label | item << kFilterDeltaLabelBits, item < the table's n); d_counts: [n], zeroed by the caller
+// before the first of the two launches; set = 0 clears the labels' bits, 1 sets them
+hipError_t launch_filter_delta_apply(const uint64_t *d_items, const uint64_t *d_recs, uint64_t n_recs, int set, unsigned long long *d_counts,
+                                     hipStream_t s) {
+  if (n_recs == 0) return hipSuccess;
+  const DeltaItem *items = reinterpret_cast<const DeltaItem *>(d_items);
+  if (set) hipLaunchKernelGGL(filter_delta_apply_kernel<true>, dim3(grid_for(n_recs)), dim3(kThreads), 0, s, items, d_recs, n_recs, d_counts);
+  else hipLaunchKernelGGL(filter_delta_apply_kernel<false>, dim3(grid_for(n_recs)), dim3(kThreads), 0, s, items, d_recs, n_recs, d_counts);
   return hipGetLastError();
 }
 

@@ -6,32 +6,13 @@
 #include <mutex>
 #include <string.h>
 
+#include "filter_lane.hpp"
 #include "kernels.hpp"
 
 namespace vk {
 namespace {
 std::atomic<uint64_t> g_next_id{1};
 
-// one build stream + pinned staging block per device, shared by the builds on it (they are short and serialise)
-struct BuildLane {
-  std::mutex mu;
-  hipStream_t stream = nullptr;
-  char *pin = nullptr;
-  size_t pin_cap = 0;
-  void *d_stage = nullptr;
-  size_t d_cap = 0;
-  unsigned long long *d_count = nullptr;
-  unsigned long long *d_partial = nullptr;   // [kPartials]: a combine's per-block bit counts
-};
-constexpr size_t kPartials = 2048;
-BuildLane *lane_of(int device) {
-  static std::mutex mu;
-  static std::vector<std::unique_ptr<BuildLane>> lanes;
-  std::lock_guard<std::mutex> lk(mu);
-  if ((size_t)device >= lanes.size()) lanes.resize((size_t)device + 1);
-  if (!lanes[(size_t)device]) lanes[(size_t)device] = std::make_unique<BuildLane>();
-  return lanes[(size_t)device].get();
-}
 // Bitmap blocks are recycled per device and size: a filter per FT.SEARCH (a predicate combined from cached terms) otherwise pays
 // a hipMalloc per copy, and -- worse -- its release a hipFree, which waits for EVERYTHING in flight on the device: the searches
 // of every other request.  Up to kPoolBytes per device wait for the next filter of their size (an index's filters are all
@@ -78,7 +59,18 @@ void pool_give(int device, size_t bytes, uint64_t *bits) {
   (void)hipSetDevice(device);
   (void)hipFree(bits);
 }
-constexpr size_t kStageBytes = (size_t)4 << 20;   // ids travel in 4 MiB pieces through pinned memory: copy k+1 is filled while k is in flight
+}  // namespace
+
+// ---- filter_lane.hpp (shared with filter_delta.cc)
+namespace filter_lane {
+BuildLane *lane_of(int device) {
+  static std::mutex mu;
+  static std::vector<std::unique_ptr<BuildLane>> lanes;
+  std::lock_guard<std::mutex> lk(mu);
+  if ((size_t)device >= lanes.size()) lanes.resize((size_t)device + 1);
+  if (!lanes[(size_t)device]) lanes[(size_t)device] = std::make_unique<BuildLane>();
+  return lanes[(size_t)device].get();
+}
 
 Status lane_ready(BuildLane *l) {
   if (!l->stream) VK_HIP_TRY(hipStreamCreateWithFlags(&l->stream, hipStreamNonBlocking));
@@ -100,10 +92,6 @@ Status stage_ensure(BuildLane *l, size_t bytes) {
   l->d_cap = want;
   return Status::Ok();
 }
-struct LaneDrain {   // see FilterSet::build
-  hipStream_t s;
-  ~LaneDrain() { (void)hipStreamSynchronize(s); }
-};
 // host words -> device through the two halves of the pinned block
 Status upload(BuildLane *l, void *d_dst, const void *h_src, size_t bytes) {
   hipEvent_t ev[2] = {nullptr, nullptr};
@@ -133,7 +121,8 @@ Status upload(BuildLane *l, void *d_dst, const void *h_src, size_t bytes) {
   (void)hipEventDestroy(ev[1]);
   return st;
 }
-}  // namespace
+}  // namespace filter_lane
+using namespace filter_lane;
 
 FilterSet::~FilterSet() {
   // (nobody reads the bitmap any more: every search that carried it held a reference until its answer was delivered)

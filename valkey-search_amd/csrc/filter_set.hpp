@@ -41,6 +41,24 @@ class FilterSet {
   // n combinations, one launch and one wait per device: out[i] = a[i] OP[i] b[i] (all of one index and one nbits)
   static Status combine_batch(const FilterSet *const *a, const FilterSet *const *b, const uint32_t *ops, uint64_t n,
                               std::vector<std::shared_ptr<FilterSet>> *out);
+  // out[i] = a NEW filter of items[i].nbits bits: a device-to-device copy of the base (nullptr = the empty set) grown with zero
+  // bits, then the labels of `clear` cleared, then the labels of `set` set (a label in both ends up set; duplicates allowed;
+  // labels >= nbits ignored).  nbits below the base's is an error: a filter never shrinks.  Every copy of the base (one per
+  // device of `devices`) gets the delta; per device the whole batch is one upload, at most three launches and one wait
+  // (filter_delta.cc).  allowed() = the base's count - bits really cleared + bits really set, counted by the delta kernel.
+  struct Delta {
+    const FilterSet *base;
+    uint64_t nbits;
+    const uint64_t *clear; uint64_t n_clear;
+    const uint64_t *set; uint64_t n_set;
+  };
+  static Status apply_delta_batch(const std::vector<int> &devices, const Delta *items, uint64_t n, std::vector<std::shared_ptr<FilterSet>> *out);
+  static Status apply_delta(const std::vector<int> &devices, const Delta &item, std::shared_ptr<FilterSet> *out) {
+    std::vector<std::shared_ptr<FilterSet>> one;
+    Status st = apply_delta_batch(devices, &item, 1, &one);
+    if (st.ok()) *out = std::move(one[0]);
+    return st;
+  }
 
  private:
   FilterSet() = default;

@@ -418,5 +418,14 @@ hipError_t launch_filter_combine(uint64_t *dst, const uint64_t *a, const uint64_
                                  hipStream_t s);   // 0 and, 1 or, 2 and-not
 // n combinations in one launch: d_items [n][4] = {dst, a, b, op} device pointers / op code, d_counts [n] zeroed (the results' bits)
 hipError_t launch_filter_combine_batch(const uint64_t *d_items, uint32_t n, uint64_t words, unsigned long long *d_counts, hipStream_t s);
+// a batch of filters derived from older ones (FilterSet::apply_delta_batch): d_items [n][kFilterDeltaItemWords] = {dst, base or
+// 0, base_words, dst_words, nbits, 0}; copy = dst <- base grown to dst_words, last word masked, slack word cleared; apply = one
+// atomic AND-NOT (set = 0) / OR (set = 1) per record (label | item << kFilterDeltaLabelBits), d_counts[item] (zeroed by the caller)
+// -= / += the bits that really changed
+constexpr uint32_t kFilterDeltaItemWords = 6;
+constexpr uint32_t kFilterDeltaLabelBits = 40;   // (FilterSet: nbits < 2^40; the item index, < 65535, sits above)
+hipError_t launch_filter_delta_copy(const uint64_t *d_items, uint32_t n, uint64_t max_dst_words, hipStream_t s);
+hipError_t launch_filter_delta_apply(const uint64_t *d_items, const uint64_t *d_recs, uint64_t n_recs, int set, unsigned long long *d_counts,
+                                     hipStream_t s);
 
 }  // namespace vk

@@ -606,6 +606,44 @@ int vk_filter_combine_batch(vk_index *ix, const vk_filter *const *a, const vk_fi
   });
 }
 
+int vk_filter_apply_delta_batch(vk_index *ix, const vk_filter_delta *items, uint64_t n, vk_filter **out) {
+  VK_NEED(ix);
+  if (n == 0) return VK_OK;
+  if (!items || !out) return fail(VK_ERR_INVALID, "NULL argument");
+  if (n > 65535) return fail(VK_ERR_INVALID, "at most 65535 derivations per call");
+  for (uint64_t i = 0; i < n; ++i) out[i] = nullptr;
+  for (uint64_t i = 0; i < n; ++i) {
+    const vk_filter_delta &it = items[i];
+    if (it.base && it.base->owner != ix) return fail(VK_ERR_INVALID, "the filter belongs to another index");
+    if (it.base && it.nbits < it.base->set->nbits()) return fail(VK_ERR_INVALID, "nbits below the base's: a filter never shrinks");
+    if ((it.n_clear && !it.clear_labels) || (it.n_set && !it.set_labels)) return fail(VK_ERR_INVALID, "NULL label list");
+  }
+  return guarded([&]() -> vk::Status {
+    std::vector<int> devs;
+    ix->impl->filter_devices(&devs);
+    // (a reference on every base for the length of the call: its handle may be released by another thread meanwhile)
+    std::vector<std::shared_ptr<vk::FilterSet>> bases(n);
+    std::vector<vk::FilterSet::Delta> d(n);
+    for (uint64_t i = 0; i < n; ++i) {
+      if (items[i].base) bases[i] = items[i].base->set;
+      d[i] = vk::FilterSet::Delta{bases[i].get(), items[i].nbits, items[i].clear_labels, items[i].n_clear, items[i].set_labels, items[i].n_set};
+    }
+    std::vector<std::shared_ptr<vk::FilterSet>> sets;
+    VK_TRY(vk::FilterSet::apply_delta_batch(devs, d.data(), n, &sets));
+    std::vector<std::unique_ptr<vk_filter>> handles(n);   // (all or nothing: an allocation failure leaves no out[i] behind)
+    for (uint64_t i = 0; i < n; ++i) handles[i].reset(new vk_filter{std::move(sets[i]), ix});
+    ix->filters.built.fetch_add(n, std::memory_order_relaxed);
+    for (uint64_t i = 0; i < n; ++i) out[i] = handles[i].release();
+    return vk::Status::Ok();
+  });
+}
+
+int vk_filter_apply_delta(vk_index *ix, const vk_filter_delta *item, vk_filter **out) {
+  VK_NEED(ix);
+  if (!item || !out) return fail(VK_ERR_INVALID, "NULL argument");
+  return vk_filter_apply_delta_batch(ix, item, 1, out);
+}
+
 void vk_filter_retain(vk_filter *f) {
   if (f) f->refs.fetch_add(1, std::memory_order_relaxed);
 }
