@@ -446,6 +446,12 @@ int vk_index_shard_count(vk_index *ix, uint32_t *out_n);
 /* the statistics of ONE shard (vk_index_get_stats of a sharded index sums the shards' cumulative counters; a per-shard
  * rate -- the slowest shard's kernel time per launch -- needs the shards' own deltas) */
 int vk_index_shard_stats(vk_index *ix, uint32_t shard, vk_index_stats *out);
+/* FLAT, f32 rows in the inner-product space (option flat-f16-image): bytes of the resident f16 image of the rows that the
+ * filter passes of the most recent batch read instead of the f32 rows -- allocated rows x padded dim x 2 (summed over the
+ * shards of a sharded index); 0 = that batch read the f32 rows (option off, L2 or bf16 index, no room on the device) or took
+ * no filter pass.  A call of its own, so that vk_index_stats keeps its size; the image is counted in
+ * vk_index_stats.device_bytes. */
+int vk_index_filter_image_bytes(vk_index *ix, uint64_t *out_bytes);
 int vk_index_shard_device_rows(vk_index *ix, uint32_t shard, uint64_t n_rows, void **d_rows, uint64_t *row_stride_bytes);
 int vk_index_shard_commit_device_rows(vk_index *ix, uint32_t shard, uint64_t n_rows, const uint64_t *labels);
 

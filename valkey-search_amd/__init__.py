@@ -127,6 +127,7 @@ def lib() -> C.CDLL:
     L.vk_index_get_option.argtypes = [vp, C.c_char_p, u64p]
     L.vk_index_search_submit.argtypes = [vp, vp, u64, u64, vp, u64, vp, i32, vp, vp, vp, SEARCH_DONE, vp]
     L.vk_index_shard_stats.argtypes = [vp, u32, C.POINTER(Stats)]
+    L.vk_index_filter_image_bytes.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.vk_index_search.argtypes = [vp, vp, u64, u64, vp, u64, vp, i32, vp, vp, u64p]
     L.vk_index_search_batch.argtypes = [vp, vp, u64, u64, u64, vp, u64, vp, i32, vp, vp, vp]
     L.vk_index_search_batch_filters.argtypes = [vp, vp, u64, u64, u64, vp, vp, vp, i32, vp, vp, vp]
@@ -256,6 +257,12 @@ class Index:
     def get_option(self, name) -> int:
         v = C.c_uint64()
         _check(lib().vk_index_get_option(self._h, name.replace("_", "-").encode(), C.byref(v)))
+        return v.value
+
+    def filter_image_bytes(self) -> int:
+        """bytes of the f16 row image the most recent batch's filter passes read (0: they read the f32 rows)"""
+        v = C.c_uint64()
+        _check(lib().vk_index_filter_image_bytes(self._h, C.byref(v)))
         return v.value
 
     def shard_stats(self, shard) -> "Stats":

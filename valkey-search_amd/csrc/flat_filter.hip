@@ -93,8 +93,13 @@ constexpr int kFAStride = 72;                // halfs per staged row: 64 + 8 pad
 // valid bounds when rows are overwritten or removed.
 // hn16 (optional, L2 indexes): per row half its squared norm, split into two f16 (hi | lo << 16) -- the extra K-step
 // that turns the filter's dot product into dot - |x|^2 / 2.
+// rows16 (optional, f32 rows in the inner-product space): the f16 image of the rows, [row][stride_e] -- every element rounded
+// to nearest even, the expression ws_rows_store applies on the way into LDS, so that the DMA row path over the image
+// multiplies exactly what the register path converts from the f32 rows.  The padding is written as it is read (zeros);
+// rows beyond hi are not written.
 __global__ __launch_bounds__(256) void row_stats_kernel(const void *rows, uint32_t bf16, uint32_t l2, uint32_t stride_e, uint32_t chunks,
-                                                        uint32_t lo, uint32_t hi, uint32_t *stats, uint32_t *tile_norm, uint32_t *hn16) {
+                                                        uint32_t lo, uint32_t hi, uint32_t *stats, uint32_t *tile_norm, uint32_t *hn16,
+                                                        _Float16 *rows16) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 3, rq = lane >> 2;
   const uint32_t total_waves = gridDim.x * 4, n_tiles = (hi - lo + kRowsPerWave - 1) / kRowsPerWave;
   float best_n2 = 0.f, best_abs = 0.f;
@@ -109,6 +114,14 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const void *rows, uint32
       n2 = fmaf(x.x, x.x, fmaf(x.y, x.y, fmaf(x.z, x.z, fmaf(x.w, x.w, n2))));
       mx = fmaxf(mx, fmaxf(fmaxf(fabsf(x.x), fabsf(x.y)), fmaxf(fabsf(x.z), fabsf(x.w))));
       bad = bad || !(x.x - x.x == 0.f) || !(x.y - x.y == 0.f) || !(x.z - x.z == 0.f) || !(x.w - x.w == 0.f);
+      if (rows16 != nullptr && row < hi) {
+        f16x4 h;
+        h[0] = (_Float16)x.x;
+        h[1] = (_Float16)x.y;
+        h[2] = (_Float16)x.z;
+        h[3] = (_Float16)x.w;
+        *reinterpret_cast<f16x4 *>(rows16 + (size_t)row * stride_e + (c * 4 + j) * 4) = h;
+      }
     }
     n2 += dpp_quad_xor1(n2);
     n2 += dpp_quad_xor2(n2);
@@ -167,13 +180,14 @@ __global__ __launch_bounds__(1024) void tile_cap_kernel(const uint32_t *tile_nor
 }
 
 hipError_t launch_row_stats(const void *rows, bool bf16, bool l2, uint32_t stride_e, uint32_t lo, uint32_t hi, uint32_t n_tiles,
-                            uint32_t *stats, uint32_t *tile_norm, uint32_t *hn16, hipStream_t s) {
+                            uint32_t *stats, uint32_t *tile_norm, uint32_t *hn16, void *rows16, hipStream_t s) {
+  if (rows16 != nullptr && bf16) return hipErrorInvalidValue;   // (bf16 rows are their own 16-bit stream)
   lo &= ~127u;                                            // whole tiles: a step of 16 rows never straddles two of them
   if (hi > lo) {
     const uint32_t tiles = (hi - lo + kRowsPerWave - 1) / kRowsPerWave;
     const uint32_t blocks = std::min<uint32_t>((tiles + 3) / 4, 2048);
     hipLaunchKernelGGL(row_stats_kernel, dim3(blocks), dim3(256), 0, s, rows, bf16 ? 1u : 0u, l2 ? 1u : 0u, stride_e, stride_e / 16, lo, hi,
-                       stats, tile_norm, hn16);
+                       stats, tile_norm, hn16, static_cast<_Float16 *>(rows16));
   }
   hipLaunchKernelGGL(tile_cap_kernel, dim3(1), dim3(1024), 0, s, tile_norm, n_tiles, stats);
   return hipGetLastError();
@@ -754,7 +768,8 @@ template <bool kBfMma> __device__ __forceinline__ f32x16 ws_mfma(f16x8 x, f16x8 
 }
 // kBfMma (bf16 rows, inner-product space): rows and queries stay bf16 -- no conversion on the way into LDS, the bf16
 // matrix-core instruction, a query rounding of 2^-8 in the margin (flat_qprep_kernel)
-// kDma (with kBfMma, final pass): the rows go HBM -> LDS directly (buffer_load ... lds), no registers and no LDS store
+// kDma (final pass; with kBfMma the bf16 rows, without it the f16 image of f32 rows -- the same bytes the register path
+// converts to, the f16 instruction, the f32 path's fragments and margin): the rows go HBM -> LDS directly (buffer_load ... lds), no registers and no LDS store
 // instructions in between.  A stage is 128 rows x 128 B without padding; the 16-byte piece c of row r sits at piece
 // c ^ ((r >> 1) & 7) of the row (the DMA writes a wave's 64 x 16 B to consecutive LDS bytes, so the swizzle is applied to
 // the SOURCE address of each lane; with it the consumers' ds_read_b128 are conflict-free).  A ring of kDmaRing stages: while
@@ -770,7 +785,7 @@ constexpr int kBRing = 3;
 template <bool kBf16, bool kL2, bool kTiming, bool kSample, int kAbl = 0, bool kBfMma = false, bool kDma = false, bool kBDma = false>
 __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
   static_assert(!kBDma || (!kDma && !kTiming && !kSample && kAbl == 0), "B by DMA: rows through registers, final pass, no experiment variants");
-  static_assert(!kDma || (kBfMma && kBf16 && !kL2 && !kSample && !kTiming), "the DMA row path serves the bf16 final pass");
+  static_assert(!kDma || (kBf16 && !kL2 && !kSample && !kTiming), "the DMA row path serves a 16-bit row stream in the final pass");
   // (experiment kernels only, kAbl != 0: a.ablate switches pieces of the pipeline OFF -- results invalid, times tell what bounds a stage:
   //  1 B producers do not store, 2 nor load; 4 row producers do not store, 8 nor load; kAbl 16 / 32: the consumers keep
   //  the B / A fragments they read first)
@@ -958,7 +973,9 @@ __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
       // of stage S+4, and the wait for B(S+1) and the rows of S+1 then leaves rows(S+2), B(S+2), rows(S+3), B(S+3) and
       // rows(S+4) -- 28 requests -- in flight: nothing is waited for earlier than it is needed.  The B stores are inline
       // assembly: behind a DMA in flight the compiler would put vmcnt(0) in front of every LDS store it knows about.
+      // (kBfMma: the bf16 rows themselves; else the f16 image of an f32 index's rows, FlatFilterArgs::rows16)
       const uint32_t pw = wave - 4;
+      const void *dma_rows = kBfMma ? a.rows : a.rows16;
       const uint32_t rpart = ((32u * pw + (lane >> 3)) * a.row_stride_f) * 2u;
       const uint32_t voff_e = rpart + (((lane & 7u) ^ (lane >> 4)) * 16u), voff_o = rpart + (((lane & 7u) ^ (4u + (lane >> 4))) * 16u);
       const uint32_t step = 8u * a.row_stride_f * 2u;
@@ -971,7 +988,7 @@ __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
 #define VK_WS_DMA_ROWS()                                                                                            \
       {                                                                                                             \
         const __amdgpu_buffer_rsrc_t r_ =                                                                           \
-            ws_rsrc(static_cast<const char *>(a.rows) + ((size_t)ld.row0 * a.row_stride_f + (size_t)ld.st * kFStageK) * 2u); \
+            ws_rsrc(static_cast<const char *>(dma_rows) + ((size_t)ld.row0 * a.row_stride_f + (size_t)ld.st * kFStageK) * 2u); \
         _Pragma("unroll") for (int u = 0; u < 4; ++u)                                                               \
           __builtin_amdgcn_raw_ptr_buffer_load_lds(r_, (__attribute__((address_space(3))) void *)(ring0 + slot_i + (pw * 4u + u) * 1024u), 16, \
                                                    (int)((u & 1) ? voff_o : voff_e), (int)(u * step), 0, 2);         \
@@ -1296,15 +1313,21 @@ __global__ __launch_bounds__(kWsThreads, 1) void flat_filter_bfmma_dma_kernel(Fl
   flat_filter_body<true, false, false, false, 0, true, true>(a);
 }
 // B operands by DMA (rows through registers): the final pass of every row format and space except the bf16 DMA kernel
-template <bool kBf16, bool kL2, bool kBfMma>
+// kImage (f32 rows, inner-product space): the pass reads the f16 image of the rows on the DMA row path instead -- under the
+// same symbol, the f32 index's final pass
+template <bool kBf16, bool kL2, bool kBfMma, bool kImage = false>
 __global__ __launch_bounds__(kWsThreads, 1) void flat_filter_bdma_kernel(FlatFilterArgs a) {
-  flat_filter_body<kBf16, kL2, false, false, 0, kBfMma, false, true>(a);
+  static_assert(!kImage || (!kBf16 && !kL2 && !kBfMma), "the f16 image belongs to f32 rows in the inner-product space");
+  if constexpr (kImage) flat_filter_body<true, false, false, false, 0, false, true>(a);
+  else flat_filter_body<kBf16, kL2, false, false, 0, kBfMma, false, true>(a);
 }
 // the early pass of a batch that walks the index in two launches (FlatFilterArgs::part_tiles): the final pass's code under its
 // own names
-template <bool kBf16, bool kL2, bool kBfMma>
+template <bool kBf16, bool kL2, bool kBfMma, bool kImage = false>
 __global__ __launch_bounds__(kWsThreads, 1) void flat_filter_early_kernel(FlatFilterArgs a) {
-  flat_filter_body<kBf16, kL2, false, false, 0, kBfMma, false, true>(a);
+  static_assert(!kImage || (!kBf16 && !kL2 && !kBfMma), "the f16 image belongs to f32 rows in the inner-product space");
+  if constexpr (kImage) flat_filter_body<true, false, false, false, 0, false, true>(a);
+  else flat_filter_body<kBf16, kL2, false, false, 0, kBfMma, false, true>(a);
 }
 __global__ __launch_bounds__(kWsThreads, 1) void flat_filter_early_bfmma_dma_kernel(FlatFilterArgs a) {
   flat_filter_body<true, false, false, false, 0, true, true>(a);
@@ -1391,6 +1414,13 @@ hipError_t launch_flat_filter(const FlatFilterArgs &a, uint32_t blocks, hipStrea
                     : (a.l2 ? reinterpret_cast<const void *>(&flat_filter_early_kernel<false, true, false>)
                             : reinterpret_cast<const void *>(&flat_filter_early_kernel<false, false, false>));
     lds = flat_filter_bdma_lds_bytes();
+  }
+  // f32 rows with a current f16 image (FlatIndex::scan_filter passes rows16 only then): both passes stream the image
+  if (a.rows16 != nullptr && a.mode == 0 && !exp_variant) {
+    if (a.bf16 || a.l2 || a.qbf16) return hipErrorInvalidValue;
+    fn = a.early ? reinterpret_cast<const void *>(&flat_filter_early_kernel<false, false, false, true>)
+                 : reinterpret_cast<const void *>(&flat_filter_bdma_kernel<false, false, false, true>);
+    lds = flat_filter_dma_lds_bytes();
   }
 #ifdef VK_EXPERIMENTS
   if (a.timing) {

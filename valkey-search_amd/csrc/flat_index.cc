@@ -279,6 +279,7 @@ class FlatIndex final : public Index {
     d_rowstats_.release();
     d_hn16_.release();
     d_tile_norm_.release();
+    d_rows16_.release();
   }
 
   Status add(uint64_t label, const float *row) override {
@@ -414,6 +415,7 @@ class FlatIndex final : public Index {
       last_filter_cands_ = 0;
       last_filter_fallback_ = 0;
       last_filter_reranked_ = 0;
+      last_filter_image_bytes_.store(0, std::memory_order_relaxed);   // (no filter pass read anything)
     }
     // caller's buffers are [nq][rq.k]
     for (uint64_t q = 0; q < rq.nq; ++q) {
@@ -524,7 +526,7 @@ class FlatIndex final : public Index {
     memset(out, 0, sizeof(*out));
     out->count = count_;
     out->capacity = capacity_;
-    out->device_bytes = store_.device_bytes();
+    out->device_bytes = store_.device_bytes() + image_bytes_.load(std::memory_order_relaxed);
     out->host_bytes = store_.host_bytes() + slot_of_.size() * 24;
     out->staged_ops = store_.staged_ops();
     out->max_level = -1;
@@ -540,6 +542,8 @@ class FlatIndex final : public Index {
     out->filter_kernel_ns = filter_ns_total_;
     return Status::Ok();
   }
+
+  uint64_t filter_image_bytes() override { return last_filter_image_bytes_.load(std::memory_order_relaxed); }
 
   void filter_devices(std::vector<int> *out) const override { out->assign(1, store_.device()); }
 
@@ -889,7 +893,9 @@ class FlatIndex final : public Index {
       VK_TRY(d_hn16_.ensure(store_.alloc_rows() * 4));
       all = true;
     }
-    if (store_.take_written(&lo, &hi) || all) {
+    const bool wrote = store_.take_written(&lo, &hi);
+    ensure_image(wrote, &all);
+    if (wrote || all) {
       // The tile norms and the bad-tile count only ever grow (atomicMax): rows that were overwritten or removed leave their
       // old maxima behind -- valid bounds, but an index that once held long or non-finite rows would keep wide gates (or stay
       // off this path) for ever.  Once the rows rewritten since the last full pass add up to a quarter of the index, start over.
@@ -904,7 +910,7 @@ class FlatIndex final : public Index {
       Status st = [&]() -> Status {
         VK_HIP_TRY(launch_row_stats(store_.d_rows(), store_.bf16(), l2(), store_.stride_f(), (uint32_t)lo, (uint32_t)hi,
                                     (uint32_t)((count_ + 127) / 128), d_rowstats_.as<uint32_t>(), d_tile_norm_.as<uint32_t>(),
-                                    l2() ? d_hn16_.as<uint32_t>() : nullptr, store_.stream()));
+                                    l2() ? d_hn16_.as<uint32_t>() : nullptr, d_rows16_.p, store_.stream()));
         uint32_t h[3] = {0, 0, 0};
         VK_HIP_TRY(hipMemcpyAsync(h, d_rowstats_.p, sizeof h, hipMemcpyDeviceToHost, store_.stream()));
         VK_HIP_TRY(hipStreamSynchronize(store_.stream()));
@@ -917,6 +923,33 @@ class FlatIndex final : public Index {
       }
     }
     return Status::Ok();
+  }
+
+  // The f16 image of the rows (f32 rows, inner-product space; option flat-f16-image): [alloc_rows + kRowSlack][Dp] f16, the
+  // bytes the filter's row producers make of the f32 rows for every batch, kept instead -- row_stats_kernel writes them for
+  // the rows a writer phase touched, and the filter's passes read 2 bytes per element by DMA.  Derived data: not saved,
+  // sized like the tile table, re-made whole after a re-allocation (*all).  It is optional: with the option off it is
+  // released here, and when the device has no room for it the refusal is remembered until the next writer phase or growth
+  // (no hipMalloc per search) and the batches are served from the f32 rows.  Called under stats_mu_.
+  void ensure_image(bool wrote, bool *all) {
+    const bool want = !store_.bf16() && !l2() && opt_.get(kOptFlatF16Image) != 0;
+    const size_t need = want ? (size_t)(store_.alloc_rows() + RowStore::kRowSlack) * store_.stride_f() * 2 : 0;
+    if (wrote || image_refused_rows_ != store_.alloc_rows()) image_refused_ = false;
+    if (d_rows16_.cap >= need && (want || d_rows16_.p == nullptr)) return;
+    if (want && image_refused_) return;
+    std::unique_lock<std::shared_mutex> lk(image_mu_);   // (no batch is between reading the pointer and enqueueing its passes)
+    d_rows16_.release();                                  // (hipFree waits for the passes already enqueued)
+    image_bytes_.store(0, std::memory_order_relaxed);
+    if (!want) return;
+    if (!d_rows16_.ensure(need).ok()) {
+      d_rows16_.release();
+      (void)hipGetLastError();   // the thread's sticky copy: the launches of this search must not find it
+      image_refused_ = true;
+      image_refused_rows_ = store_.alloc_rows();
+      return;
+    }
+    image_bytes_.store(d_rows16_.cap, std::memory_order_relaxed);
+    *all = true;
   }
 
   // K4h pipeline (flat_filter.hip), six launches for a batch that needs no hand-over:
@@ -1002,6 +1035,11 @@ class FlatIndex final : public Index {
     f.dma = (f.qbf16 && opt_.get(kOptFilterRowDma) != 0) ? 1 : 0;
     f.bdma = opt_.get(kOptFilterBDma) != 0 ? 1u : 0u;
     f.hn16 = l2() ? d_hn16_.as<uint32_t>() : nullptr;
+    // the f16 image of f32 rows (ensure_image): read by both passes of mode 0 when it is there and wanted (the option is
+    // read per batch: an A/B on one index); held shared until the passes are enqueued, against a release in between
+    std::shared_lock<std::shared_mutex> image_lk(image_mu_);
+    f.rows16 = (!store_.bf16() && !l2() && !filter_experiment && !filter_dump_active() && opt_.get(kOptFlatF16Image) != 0) ? d_rows16_.p : nullptr;
+    last_filter_image_bytes_.store(f.rows16 ? (uint64_t)store_.alloc_rows() * dp * 2 : 0, std::memory_order_relaxed);
     f.labels = store_.d_labels();
     f.allow_bits = d_allow;
     f.allow_nbits = allow_nbits;
@@ -1138,6 +1176,7 @@ class FlatIndex final : public Index {
       if (tp) VK_HIP_TRY(hipEventRecord(tp->t0, s));
       last_filter_final_rows_.store(count - (two_pass ? (uint64_t)early_tiles * filter_grid * 128 : 0), std::memory_order_relaxed);
       VK_TRY(filter_launches(fm, filter_grid));
+      image_lk.unlock();
       if (tp) {
         VK_HIP_TRY(hipEventRecord(tp->t1, s));
         tp->pending = true;
@@ -1247,6 +1286,12 @@ class FlatIndex final : public Index {
   OptRef filter_spill_chunks_{&opt_, kOptFilterSpillChunks};
   uint32_t filter_blocks_ = 0;
   DevBuf d_rowstats_, d_hn16_, d_tile_norm_;
+  DevBuf d_rows16_;                             // the f16 image of the rows (ensure_image; written under stats_mu_ + image_mu_)
+  std::shared_mutex image_mu_;
+  bool image_refused_ = false;                  // the device had no room for the image (under stats_mu_) ...
+  uint64_t image_refused_rows_ = 0;             // ... at this size of the row table
+  std::atomic<uint64_t> image_bytes_{0};        // device memory the image holds (vk_index_stats.device_bytes)
+  std::atomic<uint64_t> last_filter_image_bytes_{0};   // image bytes behind the most recent batch's passes (0: it read the f32 rows)
   std::atomic<uint32_t> filter_bad_tiles_{0};   // tiles the f16 pipe cannot carry (row_stats_kernel)
   std::mutex stats_mu_;
   uint64_t rewritten_ = 0;                      // rows brought up to date since the last full pass (under stats_mu_)

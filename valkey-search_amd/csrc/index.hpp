@@ -174,6 +174,7 @@ class Index {
   virtual Status get_row(uint64_t label, float *out) = 0;
   virtual Status contains(uint64_t label, bool *found) = 0;
   virtual Status stats(vk_index_stats *out) = 0;
+  virtual uint64_t filter_image_bytes() { return 0; }   // vk_index_filter_image_bytes (FLAT)
   virtual Status device_rows(uint64_t n, void **d_rows, uint64_t *stride_bytes) = 0;
   virtual Status commit_device_rows(uint64_t n, const uint64_t *labels) = 0;
   virtual Status save(vk_write_chunk_fn fn, void *user) = 0;

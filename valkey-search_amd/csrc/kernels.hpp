@@ -118,6 +118,10 @@ struct FlatGemmArgs {
 // K4h (flat_filter.hip): candidate stage of the batched FLAT search on the f16 matrix cores
 struct FlatFilterArgs {
   const void *rows;           // f32 or (bf16 = 1) bf16 rows, row_stride_f elements apart
+  // f32 rows, inner-product space: the f16 image of the rows, [row][row_stride_f] (row_stats_kernel keeps it current), or
+  // nullptr = none.  With it the passes of mode 0 read 2 bytes per element by DMA instead of 4 through registers; the
+  // sample pass and the re-rank keep reading `rows`.
+  const void *rows16;
   uint32_t bf16;
   uint32_t l2;                // squared Euclidean distance instead of 1 - dot
   const uint32_t *hn16;       // l2: per row |x|^2 / 2 as two f16 (hi | lo << 16), written by row_stats_kernel
@@ -219,7 +223,7 @@ bool flat_filter_supported(uint32_t row_stride_f, uint64_t k, bool bf16, bool l2
 // so far, [3] the norm cap of the sample's witnesses: the NORM |row| (f32 bits, same unit as tile_norm) that 97 % of the finite
 // tiles stay below (recomputed over n_tiles tiles)
 hipError_t launch_row_stats(const void *rows, bool bf16, bool l2, uint32_t stride_e, uint32_t lo, uint32_t hi, uint32_t n_tiles,
-                            uint32_t *stats, uint32_t *tile_norm, uint32_t *hn16, hipStream_t s);
+                            uint32_t *stats, uint32_t *tile_norm, uint32_t *hn16, void *rows16, hipStream_t s);
 hipError_t launch_flat_bound_select(const FlatBoundArgs &a, hipStream_t s);
 constexpr uint32_t kFilterMaxGroups = 16384;   // group bounds per query the selection holds in registers (8192 sample tiles)
 hipError_t launch_flat_qprep(const FlatFilterArgs &a, hipStream_t s);

@@ -582,6 +582,12 @@ class ShardedIndex final : public Index {
     return shards_[s]->contains(label, found);
   }
 
+  uint64_t filter_image_bytes() override {
+    uint64_t sum = 0;
+    for (auto &sh : shards_) sum += sh->filter_image_bytes();
+    return sum;
+  }
+
   Status stats(vk_index_stats *out) override {
     memset(out, 0, sizeof(*out));
     out->max_level = -1;

@@ -440,6 +440,15 @@ int vk_index_shard_stats(vk_index *ix, uint32_t shard, vk_index_stats *out) {
   return guarded([&] { return ix->impl->shard_stats(shard, out); });
 }
 
+int vk_index_filter_image_bytes(vk_index *ix, uint64_t *out_bytes) {
+  VK_NEED(ix);
+  if (!out_bytes) return fail(VK_ERR_INVALID, "out_bytes is NULL");
+  return guarded([&] {
+    *out_bytes = ix->impl->filter_image_bytes();
+    return vk::Status::Ok();
+  });
+}
+
 int vk_index_set_coalescing(vk_index *ix, uint32_t max_batch, uint32_t max_wait_us) {
   VK_NEED(ix);
   if (max_batch > 16384) return fail(VK_ERR_INVALID, "max_batch out of range");
