@@ -425,7 +425,8 @@ int vk_index_search_batch_filter_handles(vk_index *ix, const void *queries, uint
  * :150-162 hnsw-allow-replace-deleted / hnsw-validation-enable, :231-234 max-query-queue-depth, :363-390
  * prefiltering-threshold-ratio).  Names (csrc/options.hpp has the table with defaults and ranges), e.g.
  *   coalesce-max-batch, coalesce-max-wait-us, max-query-queue-depth, batches-in-flight, shard-ef-pct, shard-gather,
- *   kernel-timing, flat-filter, filter-spill-chunks, hnsw-visited-bytes, hnsw-pool-bytes, ...
+ *   kernel-timing, flat-filter, filter-spill-chunks, hnsw-visited-bytes, hnsw-pool-bytes, hnsw-node-mask (0 / 1; 0 releases
+ *   the masks), hnsw-node-mask-bytes, ...
  * A sharded index applies an option to itself and to every shard.  Unknown name or value out of range: VK_ERR_INVALID.
  * Options take effect for searches that START after the call; no search path reads the environment. */
 int vk_index_set_option(vk_index *ix, const char *name, uint64_t value);
@@ -452,6 +453,29 @@ int vk_index_shard_stats(vk_index *ix, uint32_t shard, vk_index_stats *out);
  * no filter pass.  A call of its own, so that vk_index_stats keeps its size; the image is counted in
  * vk_index_stats.device_bytes. */
 int vk_index_filter_image_bytes(vk_index *ix, uint64_t *out_bytes);
+/* HNSW node masks (options hnsw-node-mask, hnsw-node-mask-bytes).  A device filter is a bitmap over LABELS, the graph is
+ * walked by INTERNAL ids: per (filter, graph) the index keeps one bit per published node, "live and allowed", built on the
+ * device when a search first carries the filter and cached until a flush publishes a changed count, label or tombstone (the
+ * mask follows the GRAPH's publications, not the epoch a caller files the filter under).  Transparent behind filter handles:
+ * no answer changes; a mask that finds no room is not built and its queries test tombstone, label and filter as before.
+ * Statistics in a struct of their own (vk_index_stats keeps its size): set struct_size = sizeof(vk_node_mask_stats) before
+ * the call.  A sharded index sums its shards (one cache per shard's graph); a FLAT index reports zeros.  The masks are counted
+ * in vk_index_stats.device_bytes. */
+typedef struct vk_node_mask_stats {
+  uint64_t struct_size;
+  uint64_t masks_built;        /* masks built so far (one launch builds the missing masks of a batch) */
+  uint64_t cache_hits;         /* filters of a batch that found a current mask */
+  uint64_t evictions;          /* masks dropped to make room (stale masks dropped after a flush are not counted) */
+  uint64_t resident_entries;   /* masks in the cache now ... */
+  uint64_t resident_bytes;     /* ... and their device memory */
+  uint64_t last_batch_served;  /* queries of the most recent batch that tested a mask of their filter */
+} vk_node_mask_stats;
+int vk_index_node_mask_stats(vk_index *ix, vk_node_mask_stats *out);
+/* the node mask of filter f on a plain HNSW index, built if need be, back on the host (tests, debugging, like vk_filter_read):
+ * bit i of the words = node i (insertion order; a reused slot keeps its number) is live and its label is allowed; n_words
+ * words, zero filled past the graph's end; *out_admitted (may be NULL) = set bits, counted on the device.  Flushes first.
+ * VK_ERR_INVALID on a FLAT or a sharded index (a shard's internal ids mean nothing outside it). */
+int vk_index_node_mask_read(vk_index *ix, vk_filter *f, uint64_t *out_words, uint64_t n_words, uint64_t *out_admitted);
 int vk_index_shard_device_rows(vk_index *ix, uint32_t shard, uint64_t n_rows, void **d_rows, uint64_t *row_stride_bytes);
 int vk_index_shard_commit_device_rows(vk_index *ix, uint32_t shard, uint64_t n_rows, const uint64_t *labels);
 

@@ -62,6 +62,12 @@ class Stats(C.Structure):
                 ("last_filter_final_rows", C.c_uint64)]
 
 
+class NodeMaskStats(C.Structure):
+    """vk_node_mask_stats"""
+    _fields_ = [("struct_size", C.c_uint64), ("masks_built", C.c_uint64), ("cache_hits", C.c_uint64), ("evictions", C.c_uint64),
+                ("resident_entries", C.c_uint64), ("resident_bytes", C.c_uint64), ("last_batch_served", C.c_uint64)]
+
+
 class FilterDelta(C.Structure):
     """vk_filter_delta"""
     _fields_ = [("base", C.c_void_p), ("nbits", C.c_uint64), ("clear_labels", C.c_void_p), ("n_clear", C.c_uint64),
@@ -128,6 +134,8 @@ def lib() -> C.CDLL:
     L.vk_index_search_submit.argtypes = [vp, vp, u64, u64, vp, u64, vp, i32, vp, vp, vp, SEARCH_DONE, vp]
     L.vk_index_shard_stats.argtypes = [vp, u32, C.POINTER(Stats)]
     L.vk_index_filter_image_bytes.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.vk_index_node_mask_stats.argtypes = [vp, C.POINTER(NodeMaskStats)]
+    L.vk_index_node_mask_read.argtypes = [vp, vp, vp, u64, u64p]
     L.vk_index_search.argtypes = [vp, vp, u64, u64, vp, u64, vp, i32, vp, vp, u64p]
     L.vk_index_search_batch.argtypes = [vp, vp, u64, u64, u64, vp, u64, vp, i32, vp, vp, vp]
     L.vk_index_search_batch_filters.argtypes = [vp, vp, u64, u64, u64, vp, vp, vp, i32, vp, vp, vp]
@@ -264,6 +272,22 @@ class Index:
         v = C.c_uint64()
         _check(lib().vk_index_filter_image_bytes(self._h, C.byref(v)))
         return v.value
+
+    def node_mask_stats(self) -> NodeMaskStats:
+        """the HNSW node masks' counters (vk_index_node_mask_stats; a sharded index sums its shards)"""
+        s = NodeMaskStats()
+        s.struct_size = C.sizeof(NodeMaskStats)
+        _check(lib().vk_index_node_mask_stats(self._h, C.byref(s)))
+        return s
+
+    def node_mask_read(self, filt, n_words=None):
+        """(words, admitted): the node mask of a Filter on a plain HNSW index, built if need be -- bit i = node i (insertion
+        order) is live and its label allowed; n_words defaults to the graph's size"""
+        w = (self.stats().count + 63) // 64 if n_words is None else n_words
+        out = np.zeros(max(w, 1), np.uint64)
+        adm = C.c_uint64()
+        _check(lib().vk_index_node_mask_read(self._h, filt._h, _ptr(out), w, C.byref(adm)))
+        return out[:w], adm.value
 
     def shard_stats(self, shard) -> "Stats":
         s = Stats()

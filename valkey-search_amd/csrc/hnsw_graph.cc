@@ -475,6 +475,7 @@ Status HnswGraph::add(const float *new_row, uint64_t label, uint32_t *out_id) {
   if (slot == kNone) return insert(new_row, label, out_id);
   const uint64_t old_label = labels_[slot];
   labels_[slot] = label;
+  slot_reuses_.fetch_add(1, std::memory_order_relaxed);
   {
     std::lock_guard<std::mutex> lk(label_lookup_lock_);
     label_lookup_.erase(old_label);

@@ -58,6 +58,8 @@ class HnswGraph {
   size_t max_elements() const { return max_elements_; }
   size_t count() const { return count_.load(std::memory_order_acquire); }
   size_t deleted_count() const { return num_deleted_.load(); }
+  // tombstoned slots taken over by a new label so far (allow_replace_deleted): such a slot keeps its id and changes its label
+  uint64_t slot_reuses() const { return slot_reuses_.load(std::memory_order_relaxed); }
   int max_level() const { return maxlevel_; }
   uint32_t entry_point() const { return enterpoint_; }
   double mult() const { return mult_; }
@@ -195,6 +197,7 @@ class HnswGraph {
   size_t max_elements_;
   std::atomic<size_t> count_{0};
   std::atomic<size_t> num_deleted_{0};
+  std::atomic<uint64_t> slot_reuses_{0};
   std::atomic<uint64_t> max_label_{0};
   size_t M_, maxM_, maxM0_, efC_, ef_ = 10;
   double mult_;

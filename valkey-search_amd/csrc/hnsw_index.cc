@@ -23,6 +23,7 @@
 
 #include "hnsw_graph.hpp"
 #include "index.hpp"
+#include "node_mask_cache.hpp"
 
 namespace vk {
 
@@ -59,6 +60,8 @@ class HnswIndex final : public Index {
   }
   ~HnswIndex() override {
     (void)hipSetDevice(store_.device());
+    masks_.clear();
+    d_live_.release();
     d_links0_.release();
     d_totals_.release();
     d_upper_slot_.release();
@@ -378,7 +381,11 @@ class HnswIndex final : public Index {
     tab_nbits_ = d_tab_nbits;
     // (launch() consumes and clears them; an early return before it must not leave this batch's table behind for the
     // thread's next launch, e.g. a search_device or a device build)
-    struct TabReset { ~TabReset() { tab_ = nullptr; tab_nbits_ = nullptr; cancel_q_ = nullptr; } } tab_reset;
+    struct TabReset { ~TabReset() { tab_ = nullptr; tab_nbits_ = nullptr; cancel_q_ = nullptr; mask_one_ = nullptr; mask_tab_ = nullptr; } } tab_reset;
+    MaskUse masks;   // (held until the kernels are done: this function waits for its stream)
+    VK_TRY(prepare_masks(ctx, rq, ctx->stream, &masks));
+    mask_one_ = masks.one;
+    mask_tab_ = masks.tab;
     VK_TRY(ctx->h_out_d.ensure(rq.nq * rq.k * 4));
     VK_TRY(ctx->h_out_l.ensure(rq.nq * rq.k * 8));
     VK_TRY(ctx->h_out_n.ensure(rq.nq * 4 + 64));
@@ -454,6 +461,14 @@ class HnswIndex final : public Index {
       only.allow_tab = nullptr;   // (host bitmaps cannot come through a device-buffer call)
       Status ft = build_filter_table(ctx, only, s, &tab_, &tab_nbits_);
       if (!ft.ok()) { tab_ = nullptr; tab_nbits_ = nullptr; (void)ctx->end_async(s); return ft; }
+      // (their node masks in THIS shard's id space; the call returns with its kernels in flight: the context keeps them)
+      MaskUse masks;
+      ft = prepare_masks(ctx, only, s, &masks);
+      if (!ft.ok()) { tab_ = nullptr; tab_nbits_ = nullptr; (void)ctx->end_async(s); return ft; }
+      mask_one_ = masks.one;
+      mask_tab_ = masks.tab;
+      ctx->keep_alive.clear();
+      for (auto &r : masks.refs) ctx->keep_alive.push_back(r);
     }
     std::call_once(totals_once_, [&] {
       if (d_totals_.ensure(16).ok() && hipMemset(d_totals_.p, 0, 16) == hipSuccess) totals_zeroed_.store(true);
@@ -464,6 +479,8 @@ class HnswIndex final : public Index {
     device_totals_ = nullptr;
     tab_ = nullptr;
     tab_nbits_ = nullptr;
+    mask_one_ = nullptr;
+    mask_tab_ = nullptr;
     Status en = ctx->end_async(s);
     return st.ok() ? en : st;
   }
@@ -556,7 +573,7 @@ class HnswIndex final : public Index {
     out->staged_adds = staged_adds_.load(std::memory_order_relaxed);
     out->staged_adds_device = staged_adds_device_.load(std::memory_order_relaxed);
     out->capacity = graph_->max_elements();
-    out->device_bytes = store_.device_bytes() + d_links0_.cap + d_upper_slot_.cap + d_upper_pool_.cap;
+    out->device_bytes = store_.device_bytes() + d_links0_.cap + d_upper_slot_.cap + d_upper_pool_.cap + d_live_.cap + masks_.counters().bytes;
     out->host_bytes = store_.host_bytes() + graph_->host_bytes();
     out->staged_ops = store_.staged_ops() + staged;
     out->max_level = graph_->max_level();
@@ -584,6 +601,49 @@ class HnswIndex final : public Index {
   }
 
   void filter_devices(std::vector<int> *out) const override { out->assign(1, store_.device()); }
+
+  // hnsw-node-mask = 0 releases the masks (searches in flight keep theirs until they are done)
+  Status set_option(const char *name, uint64_t value) override {
+    VK_TRY(opt_.set(name, value));
+    if (opt_.get(kOptHnswNodeMask) == 0) {
+      (void)hipSetDevice(store_.device());
+      masks_.clear();
+    }
+    return Status::Ok();
+  }
+
+  Status node_mask_stats(vk_node_mask_stats *out) override {
+    const NodeMaskCounters c = masks_.counters();
+    out->masks_built = c.built;
+    out->cache_hits = c.hits;
+    out->evictions = c.evictions;
+    out->resident_entries = c.entries;
+    out->resident_bytes = c.bytes;
+    out->last_batch_served = last_mask_served_.load(std::memory_order_relaxed);
+    return Status::Ok();
+  }
+
+  Status node_mask_read(const FilterSet *f, uint64_t *out_words, uint64_t n_words, uint64_t *out_admitted) override {
+    VK_TRY(flush_if_dirty());
+    std::shared_lock<std::shared_mutex> lk(rw_);
+    (void)hipSetDevice(store_.device());
+    memset(out_words, 0, n_words * 8);
+    if (out_admitted) *out_admitted = 0;
+    if (pub_.count == 0) return Status::Ok();
+    CtxLease lease(pool_);
+    SearchCtx *ctx = lease.ctx;
+    SearchRequest rq;
+    rq.nq = 1;
+    rq.filter = f;
+    MaskUse masks;
+    VK_TRY(prepare_masks(ctx, rq, ctx->stream, &masks, /*for_read=*/true));
+    if (masks.refs.empty()) return Status::Err(VK_ERR_INTERNAL, "the device has no room for the node mask");
+    const NodeMask &m = *masks.refs[0];
+    const uint64_t words = std::min<uint64_t>(n_words, ((uint64_t)pub_.count + 63) / 64);
+    if (words) VK_HIP_TRY(hipMemcpy(out_words, m.bits, words * 8, hipMemcpyDeviceToHost));
+    if (out_admitted) *out_admitted = m.admitted;
+    return Status::Ok();
+  }
 
   Status device_rows(uint64_t, void **, uint64_t *) override {
     return Status::Err(VK_ERR_INVALID, "device bulk load is a FLAT-only path (the HNSW graph is built from host rows)");
@@ -674,14 +734,16 @@ class HnswIndex final : public Index {
       VK_TRY(d_upper_pool_.ensure(std::max<uint64_t>(slots + slots / 2, 64) * ups * 4));
       full = true;
     }
-    std::vector<uint32_t> dl0, dup;
+    std::vector<uint32_t> dl0, dup, touched0;
     for (uint32_t i : graph_->take_dirty_ids()) {
       if (i >= count) continue;
       uint8_t f = graph_->take_dirty(i);
+      if (f & HnswGraph::kDirtyL0) touched0.push_back(i);   // (word 0 of a level-0 list carries the tombstone)
       if (full) continue;
       if (f & HnswGraph::kDirtyL0) dl0.push_back(i);
       if (f & HnswGraph::kDirtyUpper) dup.push_back(i);
     }
+    VK_TRY(publish_live(count, cap, touched0, everything, s));
     if (full || dl0.size() > count / 8) {
       VK_HIP_TRY(hipMemcpyAsync(d_links0_.p, graph_->links0(0), (size_t)count * l0s * 4, hipMemcpyHostToDevice, s));
       dl0.clear();
@@ -739,6 +801,170 @@ class HnswIndex final : public Index {
     d_idx.release();
     VK_HIP_TRY(hipStreamSynchronize(s));
     return st;
+  }
+
+  // The live bitmap: one bit per published node, 1 = not tombstoned (HnswSearchArgs::live_bits; the first operand of every
+  // node mask).  Brought up to date where the level-0 table is published, from the nodes whose level-0 word changed since
+  // the last flush and the nodes that are new -- never a sweep of the table (except after a failed flush, when everything is
+  // republished anyway).  The host copy is the truth; the device gets the words between the first and the last one that
+  // changed.  Whatever a mask is made of -- count, a tombstone, the label of a reused slot -- bumps the publication epoch
+  // when it changes, and the masks of the old epoch are dropped.
+  Status publish_live(uint32_t count, uint64_t cap, const std::vector<uint32_t> &touched0, bool everything, hipStream_t s) {
+    const uint64_t cap_words = (cap + 63) / 64;
+    bool upload_all = everything;
+    if (d_live_.cap < cap_words * 8) {
+      VK_TRY(d_live_.ensure(cap_words * 8));
+      upload_all = true;
+    }
+    if (live_host_.size() < cap_words) live_host_.resize(cap_words, 0);
+    bool changed = count != live_count_ || everything;
+    uint64_t lo = ~0ull, hi = 0;
+    auto refresh = [&](uint32_t i) {
+      const uint64_t w = i >> 6, bit = 1ull << (i & 63);
+      const uint64_t want = graph_->is_deleted(i) ? 0 : bit;
+      if ((live_host_[w] & bit) == want) return;
+      live_host_[w] ^= bit;
+      changed = true;
+      lo = std::min(lo, w);
+      hi = std::max(hi, w);
+    };
+    if (everything) {
+      for (uint32_t i = 0; i < count; ++i) refresh(i);
+    } else {
+      for (uint32_t i : touched0)
+        if (i < live_count_) refresh(i);
+      for (uint32_t i = live_count_; i < count; ++i) refresh(i);
+    }
+    const uint64_t reuses = graph_->slot_reuses();   // a tombstoned slot under a new label: same id, same live bit, another label
+    if (reuses != seen_reuses_) changed = true;
+    const uint64_t words = ((uint64_t)count + 63) / 64;
+    if (upload_all) { lo = 0; hi = words ? words - 1 : 0; }
+    if (words && lo <= hi) VK_HIP_TRY(hipMemcpyAsync(d_live_.as<uint64_t>() + lo, live_host_.data() + lo, (hi - lo + 1) * 8, hipMemcpyHostToDevice, s));
+    live_count_ = count;
+    seen_reuses_ = reuses;
+    if (changed) {
+      mask_epoch_ += 1;
+      masks_.drop_stale(mask_epoch_);
+    }
+    return Status::Ok();
+  }
+
+  // The node masks of a batch (node_mask_cache.hpp): for every distinct device filter the batch carries, the cached mask of
+  // this publication or -- room permitting -- a new one; the new ones of the batch are built by ONE launch on its stream
+  // (node_mask.hip), which this thread waits for before the cache offers them to other streams.  A filter whose mask finds no
+  // room (hnsw-node-mask-bytes, or the device itself) gets none: its queries keep the label path.  Called under the reader
+  // lock: no flush, hence no new epoch, between here and the launch.
+  struct MaskUse {
+    std::vector<NodeMaskCache::Ref> refs;
+    const uint64_t *one = nullptr;
+    const uint64_t *const *tab = nullptr;
+  };
+  static void free_mask(void *self, uint64_t *bits) {
+    (void)hipSetDevice(static_cast<HnswIndex *>(self)->store_.device());
+    (void)hipFree(bits);   // (waits for the device: a kernel that still reads the mask is done when it returns)
+  }
+  Status prepare_masks(SearchCtx *ctx, const SearchRequest &rq, hipStream_t s, MaskUse *out, bool for_read = false) {
+    if (!for_read) last_mask_served_.store(0, std::memory_order_relaxed);
+    if (!rq.filter && !rq.filter_tab) return Status::Ok();
+    const bool on = opt_.get(kOptHnswNodeMask) != 0;
+    if (!on && !for_read) return Status::Ok();
+    const uint32_t count = pub_.count;
+    const uint64_t words = ((uint64_t)count + 63) / 64, bytes = words * 8;
+    const uint64_t epoch = mask_epoch_, budget = opt_.get(kOptHnswNodeMaskBytes);
+    const uint64_t batch = masks_.begin_batch();
+    // the distinct filters of the batch, in order of first appearance
+    std::vector<const FilterSet *> uniq;
+    std::vector<uint32_t> which(rq.filter_tab ? rq.nq : 0, ~0u);
+    if (rq.filter_tab) {
+      std::unordered_map<uint64_t, uint32_t> seen;
+      for (uint64_t q = 0; q < rq.nq; ++q) {
+        const FilterSet *f = rq.filter_tab[q];
+        if (!f) continue;
+        auto it = seen.find(f->id());
+        if (it == seen.end()) {
+          it = seen.emplace(f->id(), (uint32_t)uniq.size()).first;
+          uniq.push_back(f);
+        }
+        which[q] = it->second;
+      }
+    } else {
+      uniq.push_back(rq.filter);
+    }
+    if (uniq.empty()) return Status::Ok();
+    std::vector<NodeMaskCache::Ref> ref(uniq.size());
+    struct New { uint32_t u; uint64_t *bits; bool reserved; };
+    std::vector<New> fresh;
+    auto give_up = [&]() {   // nothing of a failed build stays behind
+      for (const New &n : fresh) {
+        (void)hipFree(n.bits);
+        if (n.reserved) masks_.unreserve(bytes);
+      }
+      fresh.clear();
+    };
+    for (uint32_t u = 0; u < uniq.size(); ++u) {
+      const uint64_t *fbits = uniq[u]->bits_on(store_.device());
+      if (!fbits) return give_up(), Status::Err(VK_ERR_INVALID, "the filter was not built for this index's device");
+      if (on) ref[u] = masks_.get(uniq[u]->id(), epoch, batch);
+      if (ref[u]) continue;
+      const bool reserved = on && masks_.reserve(bytes, budget, batch);
+      if (!reserved && !(for_read && !on)) continue;   // no room: the label path
+      void *p = nullptr;
+      if (hipMalloc(&p, bytes) != hipSuccess) {         // the device is full: likewise, and never an error
+        (void)hipGetLastError();
+        if (reserved) masks_.unreserve(bytes);
+        continue;
+      }
+      fresh.push_back(New{u, static_cast<uint64_t *>(p), reserved});
+    }
+    if (!fresh.empty()) {
+      const size_t n = fresh.size();
+      const size_t items_bytes = n * kNodeMaskItemWords * 8;
+      Status st = ctx->d_mask.ensure(items_bytes + n * 8 + rq.nq * 8);
+      if (!st.ok()) return give_up(), st;
+      std::vector<uint64_t> h(n * kNodeMaskItemWords);
+      for (size_t i = 0; i < n; ++i) {
+        h[i * kNodeMaskItemWords + 0] = reinterpret_cast<uint64_t>(uniq[fresh[i].u]->bits_on(store_.device()));
+        h[i * kNodeMaskItemWords + 1] = uniq[fresh[i].u]->nbits();
+        h[i * kNodeMaskItemWords + 2] = reinterpret_cast<uint64_t>(fresh[i].bits);
+      }
+      char *base = ctx->d_mask.as<char>();
+      unsigned long long *d_counts = reinterpret_cast<unsigned long long *>(base + items_bytes);
+      std::vector<unsigned long long> h_counts(n);
+      hipError_t e = hipMemcpyAsync(base, h.data(), items_bytes, hipMemcpyHostToDevice, s);
+      if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, n * 8, s);
+      if (e == hipSuccess)
+        e = launch_node_mask_build(store_.d_labels(), d_live_.as<uint64_t>(), count, reinterpret_cast<const uint64_t *>(base), (uint32_t)n, d_counts, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(h_counts.data(), d_counts, n * 8, hipMemcpyDeviceToHost, s);
+      if (e == hipSuccess) e = hipStreamSynchronize(s);
+      if (e != hipSuccess) return give_up(), Status::Err(VK_ERR_INTERNAL, std::string("node mask build: ") + hipGetErrorString(e));
+      for (size_t i = 0; i < n; ++i) {
+        const New &nw = fresh[i];
+        ref[nw.u] = nw.reserved ? masks_.put(uniq[nw.u]->id(), epoch, nw.bits, bytes, h_counts[i], batch)
+                                : masks_.make(uniq[nw.u]->id(), epoch, nw.bits, bytes, h_counts[i]);
+      }
+      fresh.clear();
+    }
+    uint64_t served = 0;
+    if (rq.filter_tab) {
+      bool any = false;
+      std::vector<uint64_t> h(rq.nq, 0);
+      for (uint64_t q = 0; q < rq.nq; ++q)
+        if (which[q] != ~0u && ref[which[q]]) { h[q] = reinterpret_cast<uint64_t>(ref[which[q]]->bits); served += 1; any = true; }
+      if (any) {
+        const size_t off = ((size_t)uniq.size() * (kNodeMaskItemWords + 1)) * 8;   // (behind the build's items and counts)
+        VK_TRY(ctx->d_mask.ensure(off + rq.nq * 8));
+        char *base = ctx->d_mask.as<char>();
+        VK_HIP_TRY(hipMemcpyAsync(base + off, h.data(), rq.nq * 8, hipMemcpyHostToDevice, s));
+        out->tab = reinterpret_cast<const uint64_t *const *>(base + off);
+      }
+    } else if (ref[0]) {
+      out->one = ref[0]->bits;
+      served = rq.nq;
+    }
+    for (auto &r : ref)
+      if (r) out->refs.push_back(std::move(r));
+    if (!for_read) last_mask_served_.store(served, std::memory_order_relaxed);
+    return Status::Ok();
   }
 
   // One filter per query: every distinct HOST bitmap goes to the device once, device-resident filters (filter_set.hpp) are
@@ -842,6 +1068,13 @@ class HnswIndex final : public Index {
     a.allow_nbits_tab = tab_nbits_;
     tab_ = nullptr;          // (set by search() around its launch() calls only)
     tab_nbits_ = nullptr;
+    // node masks (prepare_masks; never for the device build's out_ids searches): which launch the batch takes is decided
+    // below exactly as without them
+    a.mask_bits = out_ids ? nullptr : mask_one_;
+    a.mask_tab = out_ids ? nullptr : mask_tab_;
+    a.live_bits = !out_ids && pub_.deleted && opt_.get(kOptHnswNodeMask) != 0 ? d_live_.as<uint64_t>() : nullptr;
+    mask_one_ = nullptr;
+    mask_tab_ = nullptr;
     // (a result list beyond 2048 entries takes the LDS the frontier would need: the frontier moves to HBM then, too)
     //
     // A FEW tombstones (up to 1 / 16 of the nodes) and no filter: the frontier grows by about their share, and what keeps the
@@ -1315,6 +1548,16 @@ class HnswIndex final : public Index {
   std::shared_mutex rw_;
   std::mutex store_mu_;
   DevBuf d_links0_, d_upper_slot_, d_upper_pool_;
+  // node masks: the live bitmap (host copy = the truth, under rw_ exclusive like the tables above), the publication epoch
+  // and the cache of the masks built against it
+  DevBuf d_live_;
+  std::vector<uint64_t> live_host_;
+  uint32_t live_count_ = 0;
+  uint64_t seen_reuses_ = 0, mask_epoch_ = 1;
+  NodeMaskCache masks_{&HnswIndex::free_mask, this};
+  std::atomic<uint64_t> last_mask_served_{0};
+  static thread_local const uint64_t *mask_one_;
+  static thread_local const uint64_t *const *mask_tab_;
   std::atomic<uint64_t> last_n_eval_{0}, last_n_hops_{0}, last_overflow_{0}, last_redo_{0}, total_n_eval_{0}, total_n_hops_{0};
   static thread_local const uint64_t *const *tab_;
   static thread_local const uint64_t *tab_nbits_;
@@ -1328,6 +1571,8 @@ class HnswIndex final : public Index {
 thread_local const uint64_t *const *HnswIndex::tab_ = nullptr;
 thread_local const uint64_t *HnswIndex::tab_nbits_ = nullptr;
 thread_local const uint32_t *HnswIndex::cancel_q_ = nullptr;
+thread_local const uint64_t *HnswIndex::mask_one_ = nullptr;
+thread_local const uint64_t *const *HnswIndex::mask_tab_ = nullptr;
 thread_local unsigned long long *HnswIndex::device_totals_ = nullptr;
 
 // ---- persistence: hnswalg.h:808-865 (SaveIndex), :887-1139 (LoadIndex + loadCheck) -----------------

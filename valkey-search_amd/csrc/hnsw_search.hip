@@ -254,6 +254,15 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a) {
     // FT.SEARCH, search.cc:103-134), else the batch's
     const uint64_t *q_bits = a.allow_tab ? a.allow_tab[q] : a.allow_bits;
     const uint64_t q_nbits = a.allow_tab ? a.allow_nbits_tab[q] : a.allow_nbits;
+    // ... and its node mask, if it has one (HnswSearchArgs::mask_tab): "live and allowed" by internal id, one bit test in place
+    // of tombstone word -> label -> filter word; an unfiltered query on a graph with tombstones takes the live bitmap
+    const uint64_t *q_mask = a.mask_tab ? a.mask_tab[q] : a.mask_bits;
+    if (!q_mask && !q_bits && a.check_deleted) q_mask = a.live_bits;
+    {   // (the same for every lane: kept in scalar registers -- the kernels at the 128-register limit have no vector pair to spare)
+      const uint64_t mp = reinterpret_cast<uint64_t>(q_mask);
+      q_mask = reinterpret_cast<const uint64_t *>((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)mp) |
+                                                  ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(mp >> 32)) << 32));
+    }
     if (poll_cancel(a.cancel) || (a.cancel_q && poll_cancel(a.cancel_q + q))) {   // cancelled before this query started: an empty answer, and on to drain the queue
       for (uint32_t r = lane; r < a.k; r += kWave) { a.out_dist[(size_t)q * a.k + r] = __builtin_inff(); a.out_label[(size_t)q * a.k + r] = kNoLabel; }
       if (lane == 0) a.out_n[q] = 0;
@@ -497,8 +506,12 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a) {
     float lowerBound;
     {
       bool ep_ok = true;
-      if (a.check_deleted && (a.links0[(size_t)cur * a.l0_stride] & kDeleteFlag)) ep_ok = false;
-      if (ep_ok && q_bits && !allow_bit(q_bits, q_nbits, a.labels[cur])) ep_ok = false;
+      if (q_mask) {
+        ep_ok = (q_mask[cur >> 6] >> (cur & 63u)) & 1ull;
+      } else {
+        if (a.check_deleted && (a.links0[(size_t)cur * a.l0_stride] & kDeleteFlag)) ep_ok = false;
+        if (ep_ok && q_bits && !allow_bit(q_bits, q_nbits, a.labels[cur])) ep_ok = false;
+      }
       const float d0 = ep_ok ? curdist : kFltMax;
       if (ep_ok) {
         lowerBound = curdist;   // the reference recomputes the same distance (:378)
@@ -707,7 +720,11 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a) {
         // list order: inside it they were two dependent loads (label, bitmap word) per neighbour, one neighbour at a time
         // (hybrid shard, same lease: 31.2k -> 31.7k QPS)
         uint64_t okm = ~0ull;
-        if (a.check_deleted || q_bits) {
+        if (q_mask) {   // one independent load per neighbour
+          bool okl = true;
+          if ((m >> lane) & 1ull) okl = (q_mask[nid >> 6] >> (nid & 63u)) & 1ull;
+          okm = __ballot(okl);
+        } else if (a.check_deleted || q_bits) {
           bool okl = true;
           if ((m >> lane) & 1ull) {
             if (a.check_deleted && (a.links0[(size_t)nid * a.l0_stride] & kDeleteFlag)) okl = false;

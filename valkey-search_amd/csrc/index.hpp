@@ -6,6 +6,8 @@
 // graph's authoritative copy); the device holds the row table (row_store.hpp) and, for
 // HNSW, a fixed-stride mirror of the link lists, and answers the searches.
 #pragma once
+#include <string.h>
+
 #include <condition_variable>
 #include <memory>
 #include <mutex>
@@ -48,7 +50,11 @@ struct SearchCtx {
   hipStream_t stream = nullptr;
   DevBuf d_q, d_part_d, d_part_l, d_out_d, d_out_l, d_out_n, d_allow, d_idx, d_tmp, d_stats, d_sync, d_pool, d_pool2, d_redo,
       d_fq16, d_fthr, d_fcnt, d_fcand, d_fspill, d_fsmax, d_fpart_d, d_fpart_l,   // candidate filter (flat_filter.hip)
-      d_allow_tab;                                             // per-query filter table + the bitmaps behind it
+      d_allow_tab,                                             // per-query filter table + the bitmaps behind it
+      d_mask;                                                  // HNSW node masks: build items + counts, per-query mask table
+  // what the work enqueued last must outlive although its caller may let go of it (node masks of a device-buffer search);
+  // replaced by the context's next user
+  std::vector<std::shared_ptr<const void>> keep_alive;
   PinBuf h_q, h_out_d, h_out_l, h_out_n, h_tmp, h_idx, h_cancel;
   // per-member cancellation (SearchRequest::member_cancel): the words the kernel polls follow the batch word in h_cancel
   static constexpr size_t kMemberCancelOffset = 16;   // in u32 words
@@ -175,6 +181,16 @@ class Index {
   virtual Status contains(uint64_t label, bool *found) = 0;
   virtual Status stats(vk_index_stats *out) = 0;
   virtual uint64_t filter_image_bytes() { return 0; }   // vk_index_filter_image_bytes (FLAT)
+  // vk_index_node_mask_stats / _read (HNSW; a sharded index sums / refuses)
+  virtual Status node_mask_stats(vk_node_mask_stats *out) {
+    const uint64_t sz = out->struct_size;
+    memset(out, 0, sizeof(*out));
+    out->struct_size = sz;
+    return Status::Ok();
+  }
+  virtual Status node_mask_read(const FilterSet *, uint64_t *, uint64_t, uint64_t *) {
+    return Status::Err(VK_ERR_INVALID, "node masks are read from a plain HNSW index");
+  }
   virtual Status device_rows(uint64_t n, void **d_rows, uint64_t *stride_bytes) = 0;
   virtual Status commit_device_rows(uint64_t n, const uint64_t *labels) = 0;
   virtual Status save(vk_write_chunk_fn fn, void *user) = 0;

@@ -323,6 +323,14 @@ struct HnswSearchArgs {
   // 12 KB per wave hold about 5500 ids; ids that find no room on chip spill into the table in memory); the option's 4 = 3 whenever
   // the set fits the LDS at all (tests)
   uint32_t vis_mode;
+  // Node masks (option hnsw-node-mask; node_mask.hip): bitmaps over INTERNAL ids, one bit per published node.
+  // live_bits: 1 = not tombstoned -- non-null, a query WITHOUT a filter tests it instead of the tombstone flag in the
+  // strided level-0 record.  mask_bits (the whole batch) / mask_tab ([nq], overrides it; a null entry = none): 1 = live and
+  // allowed by the query's device filter -- a query that has one tests it instead of tombstone flag, label and filter word.
+  // A query without a mask runs exactly the code it ran before.  Never set for out_ids searches (the device build).
+  const uint64_t *live_bits;
+  const uint64_t *mask_bits;
+  const uint64_t *const *mask_tab;
 };
 // vis_mode 3: result lists in registers at up to eight slots per lane, two blocks of four waves per CU (ef up to ~450 at 768
 // dimensions) and ef x maxM0 up to the option hnsw-lds-visited-work (14400) keep the visited set in 12 KB of LDS (ids beyond its
@@ -431,5 +439,13 @@ constexpr uint32_t kFilterDeltaLabelBits = 40;   // (FilterSet: nbits < 2^40; th
 hipError_t launch_filter_delta_copy(const uint64_t *d_items, uint32_t n, uint64_t max_dst_words, hipStream_t s);
 hipError_t launch_filter_delta_apply(const uint64_t *d_items, const uint64_t *d_recs, uint64_t n_recs, int set, unsigned long long *d_counts,
                                      hipStream_t s);
+
+// node_mask.hip: n device filters translated into the graph's internal-id space in one launch.  d_items [n][kNodeMaskItemWords]
+// = {filter bits, nbits, dst} (device pointers); dst[i / 64] bit i % 64 = live bit i && label[i] < nbits && filter bit label[i],
+// every one of the (count + 63) / 64 words of dst is written (bits past count are 0); d_counts [n] (zeroed by the caller) += the
+// set bits of dst
+constexpr uint32_t kNodeMaskItemWords = 3;
+hipError_t launch_node_mask_build(const uint64_t *labels, const uint64_t *live, uint32_t count, const uint64_t *d_items, uint32_t n,
+                                  unsigned long long *d_counts, hipStream_t s);
 
 }  // namespace vk

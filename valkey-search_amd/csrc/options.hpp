@@ -44,6 +44,7 @@ enum OptId : uint32_t {
   kOptHnswOptimisticTombstones, kOptHnswDeviceBuild, kOptHnswBuildBatch, kOptHnswBuildMinGraph, kOptHnswBuildMinBatch, kOptHnswBuildFrac,
   kOptHnswBuildVerbose, kOptHnswFailpointBatch, kOptHnswPoolFloor, kOptHnswGpoolCap, kOptHnswVisitedHash, kOptHnswHashPerEf, kOptHnswHashLog2, kOptHnswVisitedMode, kOptHnswLdsWork, kOptHnswLdsWorkBig,
   kOptHnswPoolBytes, kOptHnswVisitedBytes, kOptHnswRedoBytes,
+  kOptHnswNodeMask, kOptHnswNodeMaskBytes,
   // ---- sharded index ---------------------------------------------------------------------------------------------------
   kOptShardThreads, kOptShardAllowStaged,
   kOptCount
@@ -111,6 +112,10 @@ inline const OptDesc &opt_desc(uint32_t id) {
       {"hnsw-pool-bytes", "VK_HNSW_POOL_BYTES", (uint64_t)4 << 30, 1u << 20, kMax},
       {"hnsw-visited-bytes", "VK_HNSW_VISITED_BYTES", (uint64_t)4 << 30, 1u << 20, kMax},
       {"hnsw-redo-bytes", "VK_HNSW_REDO_BYTES", (uint64_t)2 << 30, 1u << 20, kMax},
+      // device filters / tombstones by internal id: one bit test per neighbour (node_mask.hip); 0 releases the masks.  Ships off:
+      // it goes on by default only once scripts/node_mask_probe.py shows no point below the option-off median
+      {"hnsw-node-mask", "VK_HNSW_NODE_MASK", 0, 0, 1},
+      {"hnsw-node-mask-bytes", nullptr, (uint64_t)1 << 30, 0, kMax},              // ... most device memory a graph's cached masks may hold (least recently used first out)
       {"shard-threads", "VK_SHARD_THREADS", 1, 0, 1},
       {"shard-allow-staged", "VK_SHARD_ALLOW_STAGED", 0, 0, 1},
   };

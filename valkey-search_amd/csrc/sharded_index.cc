@@ -588,6 +588,27 @@ class ShardedIndex final : public Index {
     return sum;
   }
 
+  Status node_mask_stats(vk_node_mask_stats *out) override {   // one cache per shard's graph: the sum
+    const uint64_t sz = out->struct_size;
+    memset(out, 0, sizeof(*out));
+    out->struct_size = sz;
+    for (auto &sh : shards_) {
+      vk_node_mask_stats t;
+      t.struct_size = sizeof(t);
+      VK_TRY(sh->node_mask_stats(&t));
+      out->masks_built += t.masks_built;
+      out->cache_hits += t.cache_hits;
+      out->evictions += t.evictions;
+      out->resident_entries += t.resident_entries;
+      out->resident_bytes += t.resident_bytes;
+      out->last_batch_served += t.last_batch_served;
+    }
+    return Status::Ok();
+  }
+  Status node_mask_read(const FilterSet *, uint64_t *, uint64_t, uint64_t *) override {
+    return Status::Err(VK_ERR_INVALID, "a sharded index has one node mask per shard: internal ids mean nothing outside a shard");
+  }
+
   Status stats(vk_index_stats *out) override {
     memset(out, 0, sizeof(*out));
     out->max_level = -1;

@@ -449,6 +449,20 @@ int vk_index_filter_image_bytes(vk_index *ix, uint64_t *out_bytes) {
   });
 }
 
+int vk_index_node_mask_stats(vk_index *ix, vk_node_mask_stats *out) {
+  VK_NEED(ix);
+  if (!out) return fail(VK_ERR_INVALID, "out is NULL");
+  if (out->struct_size != sizeof(vk_node_mask_stats)) return fail(VK_ERR_INVALID, "vk_node_mask_stats.struct_size mismatch");
+  return guarded([&] { return ix->impl->node_mask_stats(out); });
+}
+
+int vk_index_node_mask_read(vk_index *ix, vk_filter *f, uint64_t *out_words, uint64_t n_words, uint64_t *out_admitted) {
+  VK_NEED(ix);
+  if (!f || (!out_words && n_words)) return fail(VK_ERR_INVALID, "NULL argument");
+  if (f->owner != ix) return fail(VK_ERR_INVALID, "the filter belongs to another index");
+  return guarded([&] { return ix->impl->node_mask_read(f->set.get(), out_words, n_words, out_admitted); });
+}
+
 int vk_index_set_coalescing(vk_index *ix, uint32_t max_batch, uint32_t max_wait_us) {
   VK_NEED(ix);
   if (max_batch > 16384) return fail(VK_ERR_INVALID, "max_batch out of range");
