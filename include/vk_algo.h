@@ -102,6 +102,18 @@ class Algo {
     for (uint64_t i = 0; i < n; ++i) out.emplace((dist_t)d[i], (labeltype)l[i]);
     return out;
   }
+  // ... for nq requests in hand at once (vk_index_search_labels_batch): list_begin == nullptr = one list shared by all
+  // queries, else nq + 1 offsets into labels; each queue is what searchLabels returns for that query alone
+  std::vector<ResultQueue> searchLabelsBatch(const void *queries, size_t nq, size_t k, const uint64_t *labels, const uint64_t *list_begin,
+                                             size_t n_labels) const {
+    std::vector<float> d(nq * k + 1);
+    std::vector<uint64_t> l(nq * k + 1), n(nq + 1);
+    Check(vk_index_search_labels_batch(ix_, queries, nq, k, labels, list_begin, n_labels, d.data(), l.data(), n.data()));
+    std::vector<ResultQueue> out(nq);
+    for (size_t q = 0; q < nq; ++q)
+      for (uint64_t i = 0; i < n[q]; ++i) out[q].emplace((dist_t)d[q * k + i], (labeltype)l[q * k + i]);
+    return out;
+  }
   // fstdistfunc_(query, getDataByLabel(label)) as ComputeDistanceFromRecordImpl uses it
   dist_t distance(labeltype label, const void *query) const {
     float d = 0;

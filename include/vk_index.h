@@ -292,6 +292,32 @@ int vk_index_search_batch_device(vk_index *ix, const void *d_queries, uint64_t n
 int vk_index_search_labels(vk_index *ix, const void *query, uint64_t k, const uint64_t *labels,
                            uint64_t n_labels, float *out_dist, uint64_t *out_label,
                            uint64_t *out_n);
+/* nq pre-filter searches in one device pass.  list_begin == NULL: all nq queries share labels[0 .. n_labels).
+ * Otherwise list_begin has nq + 1 ascending offsets into labels (list_begin[nq] == n_labels): query q owns
+ * labels[list_begin[q] .. list_begin[q+1]).  Outputs [nq][k] and out_n[nq]; entries past out_n[q] are
+ * (+inf, UINT64_MAX).  Query q's answer is bit for bit what vk_index_search_labels returns for it alone.
+ * The device computes every distance, finds each query's k-th smallest and hands back only the entries at or below it, in
+ * list order; the host runs the reference's heap rule over those.  A shared list is resolved to row slots once per batch.
+ * A query the device stage does not cover -- k above 4096, more ties at the k-th distance than the hand-back holds, a NaN
+ * distance, a list too long for the scratch -- is answered by vk_index_search_labels' own path after the batch.
+ * nq == 0 does nothing; k == 0 sets every out_n to 0. */
+int vk_index_search_labels_batch(vk_index *ix, const void *queries, uint64_t nq, uint64_t k,
+                                 const uint64_t *labels, const uint64_t *list_begin, uint64_t n_labels,
+                                 float *out_dist, uint64_t *out_label, uint64_t *out_n);
+/* Counters of vk_index_search_labels_batch, in a struct of their own (vk_index_stats keeps its size): set struct_size =
+ * sizeof(vk_prefilter_stats) before the call.  On a sharded index batches, queries, keys and candidates are the sums of the
+ * shards' own (a batch counts on every shard that holds one of its keys, with the keys routed there); fallback_queries
+ * counts the queries the sharded index itself sent to the per-query path. */
+typedef struct vk_prefilter_stats {
+  uint64_t struct_size;
+  uint64_t batches;            /* calls that reached the index */
+  uint64_t queries;            /* ... and their queries */
+  uint64_t keys;               /* list entries, summed over the queries (a shared list counts once per query) */
+  uint64_t candidates;         /* entries the device handed back, summed over the queries it answered */
+  uint64_t fallback_queries;   /* queries answered by the per-query path */
+  uint64_t candidate_cap;      /* entries per query the hand-back holds for the most recent batch's k (0: k not covered) */
+} vk_prefilter_stats;
+int vk_index_prefilter_stats(vk_index *ix, vk_prefilter_stats *out);
 /* fstdistfunc_(query, stored row) for one record
  * (ComputeDistanceFromRecordImpl: vector_flat.cc:256-271, vector_hnsw.cc:369-383) */
 int vk_index_distance(vk_index *ix, uint64_t label, const void *query, float *out);

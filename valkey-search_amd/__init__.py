@@ -68,6 +68,12 @@ class NodeMaskStats(C.Structure):
                 ("resident_entries", C.c_uint64), ("resident_bytes", C.c_uint64), ("last_batch_served", C.c_uint64)]
 
 
+class PrefilterStats(C.Structure):
+    """vk_prefilter_stats"""
+    _fields_ = [("struct_size", C.c_uint64), ("batches", C.c_uint64), ("queries", C.c_uint64), ("keys", C.c_uint64),
+                ("candidates", C.c_uint64), ("fallback_queries", C.c_uint64), ("candidate_cap", C.c_uint64)]
+
+
 class FilterDelta(C.Structure):
     """vk_filter_delta"""
     _fields_ = [("base", C.c_void_p), ("nbits", C.c_uint64), ("clear_labels", C.c_void_p), ("n_clear", C.c_uint64),
@@ -141,6 +147,8 @@ def lib() -> C.CDLL:
     L.vk_index_search_batch_filters.argtypes = [vp, vp, u64, u64, u64, vp, vp, vp, i32, vp, vp, vp]
     L.vk_index_search_batch_device.argtypes = [vp, vp, u64, u64, u64, vp, u64, vp, vp, vp, vp]
     L.vk_index_search_labels.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64p]
+    L.vk_index_search_labels_batch.argtypes = [vp, vp, u64, u64, vp, vp, u64, vp, vp, vp]
+    L.vk_index_prefilter_stats.argtypes = [vp, C.POINTER(PrefilterStats)]
     L.vk_index_distance.argtypes = [vp, u64, vp, f32p]
     L.vk_index_get_row.argtypes = [vp, u64, vp]
     L.vk_index_contains.argtypes = [vp, u64, C.POINTER(i32)]
@@ -514,6 +522,28 @@ class Index:
         _check(lib().vk_index_search_labels(self._h, _ptr(q), k, _ptr(labels), labels.size, _ptr(od), _ptr(ol),
                                             C.byref(n)))
         return od[:n.value].copy(), ol[:n.value].copy()
+
+    def search_labels_batch(self, Q, k, labels, list_begin=None):
+        """vk_index_search_labels_batch: nq pre-filter searches in one device pass.  list_begin=None: every query searches
+        `labels`; else nq + 1 ascending offsets into labels.  Returns (dist [nq][k], labels [nq][k], n [nq]); row q's first
+        n[q] entries are what search_labels(Q[q], k, its list) returns."""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        nq = Q.shape[0]
+        labels = np.ascontiguousarray(labels, dtype=np.uint64)
+        lb = None if list_begin is None else np.ascontiguousarray(list_begin, dtype=np.uint64)
+        assert lb is None or lb.size == nq + 1
+        od = np.empty((nq, max(k, 1)), np.float32)
+        ol = np.empty((nq, max(k, 1)), np.uint64)
+        on = np.zeros(max(nq, 1), np.uint64)
+        _check(lib().vk_index_search_labels_batch(self._h, _ptr(Q), nq, k, _ptr(labels), _ptr(lb), labels.size, _ptr(od), _ptr(ol), _ptr(on)))
+        return od[:, :k], ol[:, :k], on[:nq]
+
+    def prefilter_stats(self) -> PrefilterStats:
+        """the counters of search_labels_batch (vk_index_prefilter_stats; a sharded index sums its shards)"""
+        s = PrefilterStats()
+        s.struct_size = C.sizeof(PrefilterStats)
+        _check(lib().vk_index_prefilter_stats(self._h, C.byref(s)))
+        return s
 
     def distance(self, label, q):
         q = np.ascontiguousarray(q, dtype=np.float32)

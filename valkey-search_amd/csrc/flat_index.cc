@@ -214,24 +214,7 @@ Status upload_allow(SearchCtx *ctx, const uint64_t *allow_bits, uint64_t allow_n
 // distance is strictly smaller (ties keep what is already there).
 void prefilter_heap_select(const float *dist, const uint64_t *labels, uint64_t n, uint64_t k, float *out_dist,
                            uint64_t *out_label, uint64_t *out_n) {
-  std::priority_queue<std::pair<float, uint64_t>> results;
-  for (uint64_t i = 0; i < n; ++i) {
-    if (labels[i] == ~0ull) continue;  // unknown key: ComputeDistanceFromRecord failed
-    if (results.size() < k) {
-      results.emplace(dist[i], labels[i]);
-    } else if (k && dist[i] < results.top().first) {
-      results.pop();
-      results.emplace(dist[i], labels[i]);
-    }
-  }
-  uint64_t m = results.size();
-  *out_n = m;
-  while (m) {
-    --m;
-    out_dist[m] = results.top().first;
-    out_label[m] = results.top().second;
-    results.pop();
-  }
+  prefilter_heap_rule(dist, labels, n, k, out_dist, out_label, out_n);   // (prefilter_host.hpp: shared with the batched path)
 }
 
 // the pre-filter path on any index: per-key distances from the device, then the reference's heap rule in key order
@@ -492,6 +475,31 @@ class FlatIndex final : public Index {
     const float *hd = ctx->h_tmp.as<float>();
     for (uint64_t i = 0, j = 0; i < n; ++i)
       if (found[i]) out_dist[i] = hd[j++];
+    return Status::Ok();
+  }
+
+  Status prefilter_candidates(const float *queries, uint64_t nq, uint64_t k, const uint64_t *labels, const uint64_t *list_begin,
+                              uint64_t n_labels, PrefilterCands *out) override {
+    VK_TRY(flush_if_dirty());
+    std::shared_lock<std::shared_mutex> lk(rw_);
+    (void)hipSetDevice(store_.device());
+    CtxLease lease(pool_);
+    PrefilterResolved r;   // label -> slot once per distinct list
+    prefilter_resolve(labels, list_begin, n_labels, nq, [&](uint64_t label, uint32_t *slot) {
+      auto it = slot_of_.find(label);
+      if (it == slot_of_.end()) return false;
+      *slot = it->second;
+      return true;
+    }, &r);
+    VK_TRY(prefilter_device_stage(lease.ctx, store_.d_rows(), params_.dim, store_.stride_f(), l2(), store_.bf16(), queries, k, r, out));
+    uint64_t cands = 0;
+    for (uint64_t q = 0; q < nq; ++q)
+      if (!out->fallback[q]) cands += out->begin[q + 1] - out->begin[q];
+    pf_.batches.fetch_add(1, std::memory_order_relaxed);
+    pf_.queries.fetch_add(nq, std::memory_order_relaxed);
+    pf_.keys.fetch_add(list_begin ? n_labels : n_labels * nq, std::memory_order_relaxed);
+    pf_.candidates.fetch_add(cands, std::memory_order_relaxed);
+    pf_.candidate_cap.store(prefilter_cap(k), std::memory_order_relaxed);
     return Status::Ok();
   }
 

@@ -518,6 +518,29 @@ class HnswIndex final : public Index {
     return Status::Ok();
   }
 
+  Status prefilter_candidates(const float *queries, uint64_t nq, uint64_t k, const uint64_t *labels, const uint64_t *list_begin,
+                              uint64_t n_labels, PrefilterCands *out) override {
+    VK_TRY(flush_if_dirty());
+    std::shared_lock<std::shared_mutex> lk(rw_);
+    (void)hipSetDevice(store_.device());
+    CtxLease lease(pool_);
+    PrefilterResolved r;   // label -> slot once per distinct list
+    prefilter_resolve(labels, list_begin, n_labels, nq, [&](uint64_t label, uint32_t *slot) {
+      // tombstoned labels are "not found" (vector_hnsw.cc:55-64); so are labels not published to the device yet
+      return graph_->lookup(label, slot) && *slot < pub_.count && !graph_->is_deleted(*slot);
+    }, &r);
+    VK_TRY(prefilter_device_stage(lease.ctx, store_.d_rows(), params_.dim, store_.stride_f(), l2(), store_.bf16(), queries, k, r, out));
+    uint64_t cands = 0;
+    for (uint64_t q = 0; q < nq; ++q)
+      if (!out->fallback[q]) cands += out->begin[q + 1] - out->begin[q];
+    pf_.batches.fetch_add(1, std::memory_order_relaxed);
+    pf_.queries.fetch_add(nq, std::memory_order_relaxed);
+    pf_.keys.fetch_add(list_begin ? n_labels : n_labels * nq, std::memory_order_relaxed);
+    pf_.candidates.fetch_add(cands, std::memory_order_relaxed);
+    pf_.candidate_cap.store(prefilter_cap(k), std::memory_order_relaxed);
+    return Status::Ok();
+  }
+
   Status distance(uint64_t label, const float *query, float *out) override {
     float d;
     uint64_t l, n = 0;

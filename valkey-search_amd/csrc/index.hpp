@@ -8,6 +8,7 @@
 #pragma once
 #include <string.h>
 
+#include <atomic>
 #include <condition_variable>
 #include <memory>
 #include <mutex>
@@ -19,6 +20,7 @@
 #include "filter_set.hpp"
 #include "kernels.hpp"
 #include "options.hpp"
+#include "prefilter_host.hpp"
 #include "row_store.hpp"
 
 namespace vk {
@@ -169,6 +171,21 @@ class Index {
   // ... and its host half: AddPrefilteredKey's heap over those distances, in key order
   Status search_labels(const float *query, uint64_t k, const uint64_t *labels, uint64_t n, float *out_dist,
                        uint64_t *out_label, uint64_t *out_n);
+  // vk_index_search_labels_batch: nq pre-filter searches, each answer bit for bit search_labels' (prefilter_batch.cc).  The
+  // device stage is prefilter_candidates -- the shard-level call, candidates instead of an answer: per query every entry at
+  // or below its k-th smallest distance, in position order (positions index `labels`), or the mark "take the per-query
+  // path".  An index without a device stage marks every query.
+  Status search_labels_batch(const float *queries, uint64_t nq, uint64_t k, const uint64_t *labels, const uint64_t *list_begin,
+                             uint64_t n_labels, float *out_dist, uint64_t *out_label, uint64_t *out_n);
+  virtual Status prefilter_candidates(const float *, uint64_t nq, uint64_t, const uint64_t *, const uint64_t *, uint64_t,
+                                      PrefilterCands *out) {
+    out->reset(nq, true);
+    return Status::Ok();
+  }
+  virtual Status prefilter_stats(vk_prefilter_stats *out) {   // (a sharded index sums its shards)
+    pf_.read(out);
+    return Status::Ok();
+  }
   // sharded index: its shards (vk_index_shard_device_rows / _commit_device_rows address one of them)
   // the devices a filter of this index must be resident on (FilterSet::build)
   virtual void filter_devices(std::vector<int> *out) const = 0;
@@ -205,7 +222,28 @@ class Index {
   }
   vk_index_params params_;
   Options opt_;
+  // counters of the batched pre-filter search (vk_prefilter_stats)
+  struct PrefilterCounters {
+    std::atomic<uint64_t> batches{0}, queries{0}, keys{0}, candidates{0}, fallback_queries{0}, candidate_cap{0};
+    void read(vk_prefilter_stats *out) const {
+      const uint64_t sz = out->struct_size;
+      memset(out, 0, sizeof(*out));
+      out->struct_size = sz;
+      out->batches = batches.load(std::memory_order_relaxed);
+      out->queries = queries.load(std::memory_order_relaxed);
+      out->keys = keys.load(std::memory_order_relaxed);
+      out->candidates = candidates.load(std::memory_order_relaxed);
+      out->fallback_queries = fallback_queries.load(std::memory_order_relaxed);
+      out->candidate_cap = candidate_cap.load(std::memory_order_relaxed);
+    }
+  } pf_;
 };
+
+// The device stage of prefilter_candidates on one device, for lists already resolved to row slots (prefilter_batch.cc):
+// per chunk of queries one upload (queries, segment tables, slots), K8b, K8c, one download of the hand-back, one
+// synchronise.  The caller holds the index's shared lock and the context's lease.
+Status prefilter_device_stage(SearchCtx *ctx, const void *d_rows, uint32_t dim, uint32_t stride_f, bool l2, bool bf16, const float *queries,
+                              uint64_t k, const PrefilterResolved &r, PrefilterCands *out);
 
 // vk_index_load_tracked: the VectorTracker hook of LoadIndex (bruteforce.h:201, hnswalg.h:1000) -- set by the ABI entry
 // around the load on the loading thread, called by the loaders once per element as it is read from the stream

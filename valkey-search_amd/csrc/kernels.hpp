@@ -407,6 +407,35 @@ int flat_scan_pick_qb(uint64_t nq, uint32_t chunks, int e, bool l2);
 hipError_t launch_flat_scan(const FlatScanArgs &a, bool l2, bool bf16, int qb, int e, hipStream_t s);
 hipError_t launch_merge_topk(const MergeArgs &a, int e, uint64_t nq, hipStream_t s);
 hipError_t launch_gather_distance(const GatherArgs &a, bool l2, bool bf16, hipStream_t s);
+
+// prefilter_select.hip: the batched pre-filter search.  K8b = K8 over nq queries and a CSR of row-slot lists: a shared list
+// (seg_begin == nullptr: every query owns idx[0 .. shared_len), out is [nq][shared_len]) or one segment per query
+// (query q owns idx / out [seg_begin[q] .. seg_begin[q + 1]); tile_begin [nq + 1] = running number of 64-entry tiles,
+// prefilter_tiles() of each segment's length, n_tiles = tile_begin[nq]).
+struct PrefilterDistArgs {
+  const void *rows;
+  const float *queries;        // [nq][q_stride_f] padded
+  const uint32_t *idx;         // row slots
+  const uint32_t *seg_begin;   // [nq + 1] or nullptr
+  const uint32_t *tile_begin;  // [nq + 1] (with seg_begin)
+  float *out;
+  uint32_t row_stride_f, q_stride_f, chunks;
+  uint32_t nq, shared_len, n_tiles;
+};
+// K8c: per query, over its segment of `dist` (laid out as K8b's out): count[q] = entries at or below T = the k-th
+// smallest distance (the maximum when the segment is shorter than k), cand[q][0 .. min(count, cap)) = the first of them in
+// segment order as (index in the segment, distance bits); count[q] = 0xFFFFFFFF when the segment holds a NaN, and some
+// value above cap (not the exact number) when more than cap entries qualify.
+struct PrefilterSelectArgs {
+  const float *dist;
+  const uint32_t *seg_begin;   // [nq + 1] or nullptr (shared_len entries per query)
+  uint32_t shared_len, nq, k, cap;
+  uint32_t *count;             // [nq]
+  uint2 *cand;                 // [nq][cap]
+};
+uint32_t prefilter_tiles(uint64_t entries);
+hipError_t launch_prefilter_distance(const PrefilterDistArgs &a, bool l2, bool bf16, hipStream_t s);
+hipError_t launch_prefilter_select(const PrefilterSelectArgs &a, hipStream_t s);
 // the answer of an empty index / shard: out_n = 0, every entry (+inf, kNoLabel)
 // fused re-rank + selection of the candidate filter's survivors (k <= 64): one block per query writes the query's answer
 hipError_t launch_flat_rerank(const FlatScanArgs &a, const MergeArgs &m, bool l2, bool bf16, hipStream_t s);

@@ -565,6 +565,53 @@ class ShardedIndex final : public Index {
     return Status::Ok();
   }
 
+  // The batched pre-filter search: each list's labels routed to their shards once, each shard's device stage over its part
+  // with the same k (its k-th smallest is at or above the global one, so the union of the shards' candidates is a superset
+  // of the global {distance <= T}), the union back in the caller's order.  A query any shard hands over is handed over.
+  Status prefilter_candidates(const float *queries, uint64_t nq, uint64_t k, const uint64_t *labels, const uint64_t *list_begin,
+                              uint64_t n_labels, PrefilterCands *out) override {
+    const size_t S = shards_.size();
+    std::vector<std::vector<uint64_t>> lab(S), pos(S), begin(S);
+    {
+      std::shared_lock<std::shared_mutex> lk(rw_);
+      const uint64_t lists = list_begin ? nq : 1;
+      for (uint64_t l = 0; l < lists; ++l) {
+        for (size_t s = 0; s < S; ++s) begin[s].push_back(lab[s].size());
+        const uint64_t lo = list_begin ? list_begin[l] : 0, hi = list_begin ? list_begin[l + 1] : n_labels;
+        for (uint64_t i = lo; i < hi; ++i) {
+          auto it = route_.find(labels[i]);
+          if (it == route_.end()) continue;
+          lab[it->second].push_back(labels[i]);
+          pos[it->second].push_back(i);
+        }
+      }
+      for (size_t s = 0; s < S; ++s) begin[s].push_back(lab[s].size());
+    }
+    std::vector<PrefilterCands> parts(S);
+    for (size_t s = 0; s < S; ++s) {
+      if (lab[s].empty()) continue;   // (parts[s] stays empty: the shard holds no key of the batch)
+      VK_TRY(shards_[s]->prefilter_candidates(queries, nq, k, lab[s].data(), list_begin ? begin[s].data() : nullptr, lab[s].size(), &parts[s]));
+      if (parts[s].fallback.size() != nq || parts[s].begin.size() != nq + 1) return Status::Err(VK_ERR_INTERNAL, "prefilter: malformed shard candidates");
+      for (PrefilterCand &c : parts[s].items) c.pos = pos[s][c.pos];   // the shard's position -> the caller's
+    }
+    prefilter_union(parts, nq, out);
+    pf_.candidate_cap.store(prefilter_cap(k), std::memory_order_relaxed);
+    return Status::Ok();
+  }
+  Status prefilter_stats(vk_prefilter_stats *out) override {   // the shards' sums; the fallbacks are this index's own
+    pf_.read(out);
+    for (auto &sh : shards_) {
+      vk_prefilter_stats t;
+      t.struct_size = sizeof(t);
+      VK_TRY(sh->prefilter_stats(&t));
+      out->batches += t.batches;
+      out->queries += t.queries;
+      out->keys += t.keys;
+      out->candidates += t.candidates;
+    }
+    return Status::Ok();
+  }
+
   Status distance(uint64_t label, const float *query, float *out) override {
     uint32_t s;
     if (!route_of(label, &s)) return Status::Err(VK_ERR_NOT_FOUND, "Couldn't find internal id");

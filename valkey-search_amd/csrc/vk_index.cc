@@ -371,6 +371,32 @@ int vk_index_search_labels(vk_index *ix, const void *query, uint64_t k, const ui
   });
 }
 
+int vk_index_search_labels_batch(vk_index *ix, const void *queries, uint64_t nq, uint64_t k, const uint64_t *labels,
+                                 const uint64_t *list_begin, uint64_t n_labels, float *out_dist, uint64_t *out_label, uint64_t *out_n) {
+  // every argument error before the index is touched
+  if (!out_dist || !out_label || !out_n) return fail(VK_ERR_INVALID, "NULL output");
+  if (nq && !queries) return fail(VK_ERR_INVALID, "queries is NULL");
+  if (n_labels && !labels) return fail(VK_ERR_INVALID, "labels is NULL");
+  if (list_begin) {
+    for (uint64_t q = 0; q < nq; ++q)
+      if (list_begin[q] > list_begin[q + 1]) return fail(VK_ERR_INVALID, "list_begin is not ascending");
+    if (list_begin[nq] != n_labels) return fail(VK_ERR_INVALID, "list_begin does not end at n_labels");
+  }
+  VK_NEED(ix);
+  if (nq == 0) return VK_OK;
+  return guarded([&] {
+    return ix->impl->search_labels_batch(static_cast<const float *>(queries), nq, k, labels, list_begin, n_labels, out_dist, out_label,
+                                         out_n);
+  });
+}
+
+int vk_index_prefilter_stats(vk_index *ix, vk_prefilter_stats *out) {
+  if (!out) return fail(VK_ERR_INVALID, "out is NULL");
+  if (out->struct_size != sizeof(vk_prefilter_stats)) return fail(VK_ERR_INVALID, "vk_prefilter_stats.struct_size mismatch");
+  VK_NEED(ix);
+  return guarded([&] { return ix->impl->prefilter_stats(out); });
+}
+
 int vk_index_distance(vk_index *ix, uint64_t label, const void *query, float *out) {
   VK_NEED(ix);
   if (!query || !out) return fail(VK_ERR_INVALID, "NULL argument");
