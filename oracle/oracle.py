@@ -456,9 +456,11 @@ def prefilter_topk(space, q, rows, labels, k, isa="skylake"):
     q, rows = f32(q), f32(rows)
     labels = np.ascontiguousarray(labels, dtype=np.uint64)
     n = rows.shape[0]
-    ptrs = (_f32p * max(n, 1))()
-    for i in range(n):
-        ptrs[i] = C.cast(rows.ctypes.data + i * rows.strides[0], _f32p)
+    # the row pointers as one array (a list of millions of keys: no Python loop over it)
+    addr = np.zeros(max(n, 1), dtype=np.uint64)
+    if n:
+        addr[:] = np.uint64(rows.ctypes.data) + np.arange(n, dtype=np.uint64) * np.uint64(rows.strides[0])
+    ptrs = C.cast(addr.ctypes.data, C.POINTER(_f32p))
     od = np.empty(max(k, 1), dtype=np.float32)
     ol = np.empty(max(k, 1), dtype=np.uint64)
     m = LIB.vko_prefilter_topk(SPACE[space], ISA[isa], rows.shape[1] if n else q.size, _fp(q), ptrs,
