@@ -219,7 +219,10 @@ __global__ __launch_bounds__(64) void flat_qprep_kernel(FlatFilterArgs a) {
   for (int m = 1; m < kWave; m <<= 1) {
     n2 += __shfl_xor(n2, m);
     mx = fmaxf(mx, __shfl_xor(mx, m));
-    bad = bad || __shfl_xor((int)bad, m);
+    // (every lane takes part in the exchange: behind `bad ||` the lanes that already know would sit it out, their partners
+    //  would read an inactive lane, and a NaN -- which mx does not see -- would stay with the one lane that holds it)
+    const int bad_there = __shfl_xor((int)bad, m);
+    bad = bad || bad_there != 0;
   }
   // a query that cannot go through f16 (values beyond its range, non-finite): its products could be NaN, which passes
   // every gate -- the column gets ZERO fragments and a closed gate, and the query is handed to the exact pass, alone
@@ -1372,6 +1375,8 @@ hipError_t launch_flat_qprep(const FlatFilterArgs &a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// (tests/helpers/filter_probe.hip, filter_probe_symbol, repeats the choice of `fn` below branch by branch to name the kernel a
+//  test ran: a branch added here is added there)
 hipError_t launch_flat_filter(const FlatFilterArgs &a, uint32_t blocks, hipStream_t s) {
   if (a.nqt == 0 || a.nqt > 8 || blocks == 0 || a.n_tiles == 0 || (a.mode == 1 && a.sample_gap == 0)) return hipErrorInvalidValue;
   size_t lds = flat_filter_lds_bytes();
