@@ -82,6 +82,7 @@ namespace {
 constexpr int kFTileRows = 128;
 constexpr int kFStageK = 64;                 // k per pipeline stage: 4 MFMA K-steps of 16
 constexpr int kFAStride = 72;                // halfs per staged row: 64 + 8 pad = 144 B (conflict-free b128 reads)
+constexpr int kFAStride16 = 80;              // ... of the kernels that multiply with 16x16x32: 160 B (144 B is 2-way conflicted for their reads)
 }  // namespace
 
 // ---- row statistics: the largest row norm per 128-row tile (and of the index) over rows [lo, hi) ------------------------
@@ -699,11 +700,11 @@ __device__ __forceinline__ void ws_rows_load_sample(WsRows<kBf16> &s, const Flat
 }
 // -> f16 in LDS.  f32 rows: round to nearest even.  bf16 rows: bf16 -> f32 is a shift and f32 -> f16 is then EXACT for
 // every value in f16's normal range (8 significant bits fit 11), so a bf16 index carries no row rounding error at all.
-template <bool kBf16, bool kL2, bool kSample, bool kBfMma = false>
+template <bool kBf16, bool kL2, bool kSample, bool kBfMma = false, int kStride = kFAStride>
 __device__ __forceinline__ void ws_rows_store(_Float16 *buf, uint32_t *hn_buf, uint32_t t, const WsRows<kBf16> &s, bool raw = false) {
   if constexpr (kL2) hn_buf[t] = s.hn;
   if constexpr (kBf16) {
-    _Float16 *dst = buf + (t >> 3) * kFAStride + (t & 7) * 8;
+    _Float16 *dst = buf + (t >> 3) * kStride + (t & 7) * 8;
     if (kBfMma || raw) {   // bf16 matrix-core path: the bytes as they are (raw: the same as an experiment of the f16 path)
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
@@ -711,7 +712,7 @@ __device__ __forceinline__ void ws_rows_store(_Float16 *buf, uint32_t *hn_buf, u
         if constexpr (kSample) {
           if ((t & 7) == 0 && ((s.pz >> u) & 1u)) v[0] = (v[0] & 0xFFFF0000u) | 0x7FC0u;   // bf16 NaN: no witness
         }
-        *reinterpret_cast<u32x4v *>(dst + u * 16 * kFAStride) = v;
+        *reinterpret_cast<u32x4v *>(dst + u * 16 * kStride) = v;
       }
       return;
     }
@@ -726,10 +727,10 @@ __device__ __forceinline__ void ws_rows_store(_Float16 *buf, uint32_t *hn_buf, u
       if constexpr (kSample) {
         if ((t & 7) == 0 && ((s.pz >> u) & 1u)) h[0] = __builtin_bit_cast(_Float16, (uint16_t)0x7E00);   // NaN: no witness
       }
-      *reinterpret_cast<f16x8 *>(dst + u * 16 * kFAStride) = h;
+      *reinterpret_cast<f16x8 *>(dst + u * 16 * kStride) = h;
     }
   } else {
-    _Float16 *dst = buf + (t >> 4) * kFAStride + (t & 15) * 4;
+    _Float16 *dst = buf + (t >> 4) * kStride + (t & 15) * 4;
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
       f16x4 h;
@@ -740,7 +741,7 @@ __device__ __forceinline__ void ws_rows_store(_Float16 *buf, uint32_t *hn_buf, u
       if constexpr (kSample) {
         if ((t & 15) == 0 && ((s.pz >> u) & 1u)) h[0] = __builtin_bit_cast(_Float16, (uint16_t)0x7E00);   // NaN: no witness
       }
-      *reinterpret_cast<f16x4 *>(dst + u * 8 * kFAStride) = h;
+      *reinterpret_cast<f16x4 *>(dst + u * 8 * kStride) = h;
     }
   }
 }
@@ -769,6 +770,10 @@ template <bool kBfMma> __device__ __forceinline__ f32x16 ws_mfma(f16x8 x, f16x8 
   if constexpr (kBfMma) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, x), __builtin_bit_cast(bf16x8, y), c, 0, 0, 0);
   else return __builtin_amdgcn_mfma_f32_32x32x16_f16(x, y, c, 0, 0, 0);
 }
+template <bool kBfMma> __device__ __forceinline__ f32x4v ws_mfma16(f16x8 x, f16x8 y, f32x4v c) {
+  if constexpr (kBfMma) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, x), __builtin_bit_cast(bf16x8, y), c, 0, 0, 0);
+  else return __builtin_amdgcn_mfma_f32_16x16x32_f16(x, y, c, 0, 0, 0);
+}
 // kBfMma (bf16 rows, inner-product space): rows and queries stay bf16 -- no conversion on the way into LDS, the bf16
 // matrix-core instruction, a query rounding of 2^-8 in the margin (flat_qprep_kernel)
 // kDma (final pass; with kBfMma the bf16 rows, without it the f16 image of f32 rows -- the same bytes the register path
@@ -785,8 +790,97 @@ constexpr uint32_t kDmaStageBytes = kFTileRows * 128;
 // and no registers, no LDS store instructions (which were most of what the B operands cost a stage: the VGPR -> LDS path
 // moves ~80 B per clock, 410 clocks for a 32 KB stage).  The query producers only issue the requests.
 constexpr int kBRing = 3;
-template <bool kBf16, bool kL2, bool kTiming, bool kSample, int kAbl = 0, bool kBfMma = false, bool kDma = false, bool kBDma = false>
+// The gate of the 16x16x32 consumers.  Register reg of row subtile rs (16 rows) is row rs*16 + 4*kg + reg of the tile, column
+// c of the wave's query sixteenth qs: a lane owns FOUR query columns, wave*64 + 16 qs + c, and 32 rows of each.  The same
+// structure as filter_gate: one max per column, one vote for the wave, then one per 128 x 16 block; bit rs*4 + reg of a
+// lane's mask is its passing register.  The gate's coefficients would be twelve registers a lane: lane l keeps those of ONE
+// column, wave*64 + l, works out its threshold for the tile, and the four a lane needs come from lanes 16 qs + c.
+template <bool kL2>
+__device__ __forceinline__ void filter_gate16(const FlatFilterArgs &a, const f32x4v (&acc)[4][8], const GateCol<kL2> &col, uint32_t norm_bits,
+                                              uint32_t tile_row0, uint32_t wave, uint32_t c, uint32_t kg, SurvivorRing &ring, uint32_t lane) {
+  const float thr_own = gate_thr<kL2>(col, norm_bits);
+  float thr[4];
+#pragma unroll
+  for (int qs = 0; qs < 4; ++qs) thr[qs] = __shfl(thr_own, qs * 16 + (int)c);
+#ifdef VK_EXPERIMENTS
+  if (a.dump_scores != nullptr && tile_row0 < a.dump_rows) {   // margin audit: what this gate sees, for the test to judge
+#pragma unroll
+    for (int qs = 0; qs < 4; ++qs) {
+      const uint32_t q = wave * 64 + qs * 16 + c;
+      if (q < a.nq && q < a.dump_ld) {
+#pragma unroll
+        for (int rs = 0; rs < 8; ++rs)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const uint32_t row = tile_row0 + rs * 16 + 4 * kg + r;
+            if (row < a.dump_rows) a.dump_scores[(size_t)row * a.dump_ld + q] = acc[qs][rs][r];
+          }
+      }
+    }
+    if (wave * 64 + lane < a.nq && wave * 64 + lane < a.dump_ld) a.dump_thr[(size_t)(tile_row0 / 128u) * a.dump_ld + wave * 64 + lane] = thr_own;
+  }
+#endif
+  // (fmaxf drops NaNs; they only occur in a tile outside f16, whose thr is -inf: "not below" then holds for any m)
+  float mx[4];
+  bool any = false;
+#pragma unroll
+  for (int qs = 0; qs < 4; ++qs) {
+    mx[qs] = acc[qs][0][0];
+#pragma unroll
+    for (int i = 1; i < 32; ++i) mx[qs] = fmaxf(mx[qs], acc[qs][i >> 2][i & 3]);
+    any = any || !(mx[qs] < thr[qs]);
+  }
+  if (__builtin_amdgcn_ballot_w64(any) == 0) return;
+#pragma unroll
+  for (int qs = 0; qs < 4; ++qs) {
+    const float m = mx[qs], t = thr[qs];
+    if (__builtin_amdgcn_ballot_w64(!(m < t)) == 0) continue;   // (rare: a survivor somewhere in this 128 x 16 block)
+    const uint32_t q = wave * 64 + qs * 16 + c;
+    uint32_t mk = 0;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) mk |= !(acc[qs][i >> 2][i & 3] < t) ? 1u << i : 0u;
+    if (q >= a.nq) mk = 0;
+    // (... or whose one passing register is not its maximum: a NaN, which fmaxf dropped)
+    const bool multi = __builtin_amdgcn_ballot_w64(__builtin_popcount(mk) > 1 || (mk != 0 && m < t)) != 0;
+    while (__builtin_amdgcn_ballot_w64(mk != 0) != 0) {
+      const uint32_t r = mk != 0 ? (uint32_t)__builtin_ctz(mk) : 0u;
+      const uint32_t row = tile_row0 + (r >> 2) * 16 + 4 * kg + (r & 3);
+      bool pass = mk != 0 && row < a.n_rows;
+      if (pass && a.allow_bits != nullptr) pass = allow_bit(a.allow_bits, a.allow_nbits, a.labels[row]);
+      // the pair's approximate score: a lane with ONE passing register holds it already (filter_gate)
+      float score = m;
+      if (multi) {
+#pragma unroll
+        for (int i = 0; i < 32; ++i) score = r == (uint32_t)i ? acc[qs][i >> 2][i & 3] : score;
+      }
+      mk &= mk - 1;
+      const uint64_t pm = __builtin_amdgcn_ballot_w64(pass);
+      if (pm != 0) {
+        const uint32_t n = (uint32_t)__popcll(pm);
+        if (ring.cnt + n > kWave) ring_flush(a, ring, lane);
+        if (pass) {
+          const uint32_t at = ring.cnt + (uint32_t)__popcll(pm & ((1ull << lane) - 1ull));
+          ring.ent[at * 3] = q;
+          ring.ent[at * 3 + 1] = row;
+          ring.ent[at * 3 + 2] = __float_as_uint(score);
+        }
+        ring.cnt += n;
+      }
+    }
+  }
+}
+
+// kM16 (final pass, inner-product space, FlatFilterArgs::mfma16): the consumers multiply with v_mfma_f32_16x16x32 instead
+// of 32x32x16 -- the same 128 rows x 64 queries per wave, the same LDS images and bytes read per stage, twice as many
+// instructions of half the size.  Under matrix-core load the chip holds a higher clock with the smaller shape; nothing
+// else differs: producers, rings and barriers are the other kernels'.  (Rows through registers: a 160-B row stride in
+// LDS, kFAStride16.)
+template <bool kBf16, bool kL2, bool kTiming, bool kSample, int kAbl = 0, bool kBfMma = false, bool kDma = false, bool kBDma = false,
+          bool kM16 = false>
 __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
+  static_assert(!kM16 || ((kDma || kBDma) && !kL2 && !kSample && !kTiming && kAbl == 0), "16x16x32: final pass, inner-product space, no experiment variants");
+  static_assert(!kM16 || kDma || !kBf16, "16x16x32 with the rows through registers: f32 rows");
+  constexpr int kAStride = kM16 ? kFAStride16 : kFAStride;
   static_assert(!kBDma || (!kDma && !kTiming && !kSample && kAbl == 0), "B by DMA: rows through registers, final pass, no experiment variants");
   static_assert(!kDma || (kBf16 && !kL2 && !kSample && !kTiming), "the DMA row path serves a 16-bit row stream in the final pass");
   // (experiment kernels only, kAbl != 0: a.ablate switches pieces of the pipeline OFF -- results invalid, times tell what bounds a stage:
@@ -794,7 +888,7 @@ __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
   //  the B / A fragments they read first)
   const uint32_t abl = kAbl != 0 ? exp_ablate(a) : 0u;
   extern __shared__ _Float16 lds_a[];
-  constexpr uint32_t kBufHalfs = kFTileRows * kFAStride;                    // one A stage
+  constexpr uint32_t kBufHalfs = kFTileRows * kAStride;                     // one A stage
   uint4 *lds_b = reinterpret_cast<uint4 *>(lds_a + (kDma ? kDmaRing * kDmaStageBytes / 2 : 2 * kBufHalfs));   // [2][kWsBStage]
   uint32_t *lds_ring = reinterpret_cast<uint32_t *>(lds_b + (kBDma ? kBRing : 2) * kWsBStage); // [4 consumer waves][3][64]
   uint32_t *hn_lds = lds_ring + 4 * kRingWords;                              // [2][128] (kL2)
@@ -1093,7 +1187,7 @@ __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
       VK_WS_ROWS_LOAD(x5)
       fpos_advance(ld, stages);
     }
-    ws_rows_store<kBf16, kL2, kSample, kBfMma>(lds_a, hn_lds, t, x0);
+    ws_rows_store<kBf16, kL2, kSample, kBfMma, kAStride>(lds_a, hn_lds, t, x0);
     VK_WS_PBARRIER()
     uint32_t ppar = 0;                                                       // S & 1
     unsigned long long ph[4] = {0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
@@ -1109,7 +1203,7 @@ __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
       __builtin_amdgcn_sched_barrier(0);                                                                            \
       VK_WS_TICK(0)                                                                                                 \
       ppar ^= 1;                                                                                                    \
-      if (!(abl & 4u)) ws_rows_store<kBf16, kL2, kSample, kBfMma>(lds_a + ppar * kBufHalfs, hn_lds + ppar * kFTileRows, t, RSTORE, (abl & 512u) != 0); \
+      if (!(abl & 4u)) ws_rows_store<kBf16, kL2, kSample, kBfMma, kAStride>(lds_a + ppar * kBufHalfs, hn_lds + ppar * kFTileRows, t, RSTORE, (abl & 512u) != 0); \
       else if (abl & 1024u) {   /* (experiment: wait for the stage's rows, neither convert nor store them) */      \
         _Pragma("unroll") for (int u_ = 0; u_ < (kBf16 ? 8 : 16); ++u_) asm volatile("" ::"v"(RSTORE.v[u_]));       \
       }                                                                                                             \
@@ -1174,6 +1268,21 @@ __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
       col[t2].bound = (closed[t2] || abl != 0) ? __builtin_inff() : a.qbound[jc];   // (experiments: nothing survives)
     }
   }
+  // (kM16: lane = (c, kg) = (query column of a sixteenth, k group of 8 / row group of 4); the lane keeps the gate of column
+  //  wave*64 + lane, filter_gate16)
+  const uint32_t c16 = lane & 15, kg16 = lane >> 4;
+  GateCol<kL2> col16;
+  f32x4v acc16[4][8];
+  const f32x4v zero4 = {0.f, 0.f, 0.f, 0.f};
+  {
+    const bool have = kM16 && wave * 2 + (lane >> 5) < a.nqt;
+    const uint32_t jc = have ? wave * 64 + lane : 0u;
+    const float4 co = a.qcoef[jc];
+    if constexpr (kL2) col16.c2 = co.x;
+    col16.c1 = co.y;
+    col16.c0 = co.z;
+    col16.bound = (!have || co.w != 0.f) ? __builtin_inff() : a.qbound[jc];
+  }
   f32x16 acc[2][4];
   const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -1229,6 +1338,42 @@ __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
     __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);                                                              \
     __builtin_amdgcn_sched_group_barrier(0x008, 16, 0);                                                             \
   }
+  // 16x16x32: a stage is two K-steps of 32.  Row subtile rs (16 rows), lane (c, kg): the A fragment is piece 4 s + kg of row
+  // rs*16 + c (kDma: at piece ^ swizzle(row), and the swizzle of row rs*16 + c is that of c), the B fragment of sixteenth qs
+  // = half qs & 1 of query tile qs >> 1 is slot [2 s + (kg >> 1)][(kg & 1) * 32 + 16 (qs & 1) + c] of the tile's stage.
+  // The fragments of K-step 1 are fetched as those of K-step 0 are used up: A into the registers a subtile leaves behind (K-step
+  // 0 goes subtile by subtile), B -- two sixteenths ahead, two into the registers K-step 0's leave -- in the order K-step 1, which
+  // goes sixteenth by sixteenth, takes them: fourteen fragments at the most, 56 registers beside the 128 accumulators.
+#define VK_WS_A16(RS, S)                                                                                            \
+  (kDma ? *reinterpret_cast<const f16x8 *>(dma_ab + (dma_off16 ^ ((S) * 64u)) + (RS) * 2048)                         \
+        : *reinterpret_cast<const f16x8 *>(ab16 + (RS) * 16 * kAStride + (S) * 32))
+#define VK_WS_B16(QS, S) bb16[(((QS) >> 1) * 4 + 2 * (S)) * kWave + ((QS) & 1) * 16]
+#define VK_WS_STAGE16(C0)                                                                                           \
+  {                                                                                                                 \
+    f16x8 fa[8], fb[4], fc[2];                                                                                      \
+    _Pragma("unroll") for (int rs = 0; rs < 8; ++rs) fa[rs] = VK_WS_A16(rs, 0);                                     \
+    _Pragma("unroll") for (int qs = 0; qs < 4; ++qs) fb[qs] = VK_WS_B16(qs, 0);                                     \
+    fc[0] = VK_WS_B16(0, 1);                                                                                        \
+    fc[1] = VK_WS_B16(1, 1);                                                                                        \
+    _Pragma("unroll") for (int rs = 0; rs < 8; ++rs) {                                                              \
+      _Pragma("unroll") for (int qs = 0; qs < 4; ++qs) acc16[qs][rs] = ws_mfma16<kBfMma>(fa[rs], fb[qs], C0);       \
+      fa[rs] = VK_WS_A16(rs, 1);                                                                                    \
+    }                                                                                                               \
+    fb[2] = VK_WS_B16(2, 1);                                                                                        \
+    fb[3] = VK_WS_B16(3, 1);                                                                                        \
+    _Pragma("unroll") for (int qs = 0; qs < 4; ++qs)                                                                \
+      _Pragma("unroll") for (int rs = 0; rs < 8; ++rs)                                                              \
+        acc16[qs][rs] = ws_mfma16<kBfMma>(fa[rs], qs < 2 ? fc[qs] : fb[qs], acc16[qs][rs]);                         \
+    __builtin_amdgcn_sched_group_barrier(0x100, 14, 0);                                                             \
+    _Pragma("unroll") for (int rs = 0; rs < 7; ++rs) {                                                              \
+      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                                                            \
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                                            \
+    }                                                                                                               \
+    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                                                              \
+    __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);                                                              \
+    __builtin_amdgcn_sched_group_barrier(0x008, 32, 0);                                                             \
+  }
+  const uint32_t dma_off16 = c16 * 128u + ((kg16 ^ ((c16 >> 1) & 7u)) * 16u);
   f16x8 abl_a[4], abl_b[2];
   if constexpr (kAbl != 0) {
 #pragma unroll
@@ -1246,7 +1391,22 @@ __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
     const _Float16 *ab = lds_a + par * kBufHalfs + li * kFAStride + g * 8;
     const char *dma_ab = reinterpret_cast<const char *>(lds_a) + dma_slot;
     const f16x8 *bb = reinterpret_cast<const f16x8 *>(lds_b + (kBDma ? b_slot : par * kWsBStage) + (wave * 2) * 4 * kWave) + lane;
-    if (has_q) {
+    const _Float16 *ab16 = lds_a + par * kBufHalfs + c16 * kAStride + kg16 * 8;
+    const f16x8 *bb16 = reinterpret_cast<const f16x8 *>(lds_b + (kBDma ? b_slot : par * kWsBStage) + (wave * 2) * 4 * kWave) +
+                        (kg16 >> 1) * kWave + (kg16 & 1) * 32 + c16;
+    if constexpr (kM16) {
+      if (has_q) {
+        // (the two copies start differently on purpose: what they had in common would be merged in front of the branch,
+        //  every fragment read of the stage among it, out of reach of the order the stage asks for)
+        if (st_c == 0) {
+          asm volatile("; first stage of a tile" ::: "memory");
+          VK_WS_STAGE16(zero4)
+        } else {
+          asm volatile("; stage" ::: "memory");
+          VK_WS_STAGE16(acc16[qs][rs])
+        }
+      }
+    } else if (has_q) {
       if (st_c == 0) VK_WS_STAGE(VK_WS_MMZ) else VK_WS_STAGE(VK_WS_MM)
       if constexpr ((kAbl & 128) != 0) VK_WS_STAGE(VK_WS_MM)   // (experiment: a stage's MFMAs twice per barrier)
       if constexpr (kL2) {
@@ -1276,6 +1436,8 @@ __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
         } else if constexpr ((kAbl & 64) != 0) {   // (experiment: no gate; the accumulators stay alive)
 #pragma unroll
           for (int rt = 0; rt < 4; ++rt) asm volatile("" ::"v"(acc[0][rt]), "v"(acc[1][rt]));
+        } else if constexpr (kM16) {
+          filter_gate16<kL2>(a, acc16, col16, norm_bits, tile_row0, wave, c16, kg16, ring, lane);
         } else {
           filter_gate<4, false>(a, acc[0], gate_thr<kL2>(col[0], norm_bits), tile_row0, wave * 2, li, g, ring, lane);
           filter_gate<4, false>(a, acc[1], gate_thr<kL2>(col[1], norm_bits), tile_row0, wave * 2 + 1, li, g, ring, lane);
@@ -1294,6 +1456,9 @@ __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
 #undef VK_WS_MM
 #undef VK_WS_MMZ
 #undef VK_WS_STAGE
+#undef VK_WS_STAGE16
+#undef VK_WS_A16
+#undef VK_WS_B16
 #undef VK_WS_TILE_END
 #undef VK_WS_TICK
   if constexpr (timing) {
@@ -1315,22 +1480,31 @@ __global__ __launch_bounds__(kWsThreads, 1) void flat_filter_bfmma_kernel(FlatFi
 __global__ __launch_bounds__(kWsThreads, 1) void flat_filter_bfmma_dma_kernel(FlatFilterArgs a) {
   flat_filter_body<true, false, false, false, 0, true, true>(a);
 }
+// ... with the 16x16x32 consumers (FlatFilterArgs::mfma16), and the early pass of that
+__global__ __launch_bounds__(kWsThreads, 1) void flat_filter_bfmma_dma_m16_kernel(FlatFilterArgs a) {
+  flat_filter_body<true, false, false, false, 0, true, true, false, true>(a);
+}
+__global__ __launch_bounds__(kWsThreads, 1) void flat_filter_early_bfmma_dma_m16_kernel(FlatFilterArgs a) {
+  flat_filter_body<true, false, false, false, 0, true, true, false, true>(a);
+}
 // B operands by DMA (rows through registers): the final pass of every row format and space except the bf16 DMA kernel
 // kImage (f32 rows, inner-product space): the pass reads the f16 image of the rows on the DMA row path instead -- under the
 // same symbol, the f32 index's final pass
-template <bool kBf16, bool kL2, bool kBfMma, bool kImage = false>
+template <bool kBf16, bool kL2, bool kBfMma, bool kImage = false, bool kM16 = false>
 __global__ __launch_bounds__(kWsThreads, 1) void flat_filter_bdma_kernel(FlatFilterArgs a) {
   static_assert(!kImage || (!kBf16 && !kL2 && !kBfMma), "the f16 image belongs to f32 rows in the inner-product space");
-  if constexpr (kImage) flat_filter_body<true, false, false, false, 0, false, true>(a);
-  else flat_filter_body<kBf16, kL2, false, false, 0, kBfMma, false, true>(a);
+  static_assert(!kM16 || (!kBf16 && !kL2 && !kBfMma), "16x16x32: f32 rows in the inner-product space, image and register path alike");
+  if constexpr (kImage) flat_filter_body<true, false, false, false, 0, false, true, false, kM16>(a);
+  else flat_filter_body<kBf16, kL2, false, false, 0, kBfMma, false, true, kM16>(a);
 }
 // the early pass of a batch that walks the index in two launches (FlatFilterArgs::part_tiles): the final pass's code under its
 // own names
-template <bool kBf16, bool kL2, bool kBfMma, bool kImage = false>
+template <bool kBf16, bool kL2, bool kBfMma, bool kImage = false, bool kM16 = false>
 __global__ __launch_bounds__(kWsThreads, 1) void flat_filter_early_kernel(FlatFilterArgs a) {
   static_assert(!kImage || (!kBf16 && !kL2 && !kBfMma), "the f16 image belongs to f32 rows in the inner-product space");
-  if constexpr (kImage) flat_filter_body<true, false, false, false, 0, false, true>(a);
-  else flat_filter_body<kBf16, kL2, false, false, 0, kBfMma, false, true>(a);
+  static_assert(!kM16 || (!kBf16 && !kL2 && !kBfMma), "16x16x32: f32 rows in the inner-product space, image and register path alike");
+  if constexpr (kImage) flat_filter_body<true, false, false, false, 0, false, true, false, kM16>(a);
+  else flat_filter_body<kBf16, kL2, false, false, 0, kBfMma, false, true, kM16>(a);
 }
 __global__ __launch_bounds__(kWsThreads, 1) void flat_filter_early_bfmma_dma_kernel(FlatFilterArgs a) {
   flat_filter_body<true, false, false, false, 0, true, true>(a);
@@ -1355,8 +1529,8 @@ __global__ __launch_bounds__(kWsThreads, 1) void flat_filter_sample_kernel(FlatF
 size_t flat_filter_dma_lds_bytes() {
   return (size_t)kDmaRing * kDmaStageBytes + (size_t)2 * kWsBStage * 16 + (size_t)4 * kRingWords * 4 + (size_t)2 * kFTileRows * 4 + 16;
 }
-size_t flat_filter_bdma_lds_bytes() {
-  return (size_t)2 * kFTileRows * kFAStride * sizeof(_Float16) + (size_t)kBRing * kWsBStage * 16 + (size_t)4 * kRingWords * 4 +
+size_t flat_filter_bdma_lds_bytes(bool m16) {
+  return (size_t)2 * kFTileRows * (m16 ? kFAStride16 : kFAStride) * sizeof(_Float16) + (size_t)kBRing * kWsBStage * 16 + (size_t)4 * kRingWords * 4 +
          (size_t)2 * kFTileRows * 4 + 16;
 }
 size_t flat_filter_lds_bytes() {
@@ -1418,7 +1592,7 @@ hipError_t launch_flat_filter(const FlatFilterArgs &a, uint32_t blocks, hipStrea
                             : reinterpret_cast<const void *>(&flat_filter_early_kernel<true, false, false>))
                     : (a.l2 ? reinterpret_cast<const void *>(&flat_filter_early_kernel<false, true, false>)
                             : reinterpret_cast<const void *>(&flat_filter_early_kernel<false, false, false>));
-    lds = flat_filter_bdma_lds_bytes();
+    lds = flat_filter_bdma_lds_bytes(false);
   }
   // f32 rows with a current f16 image (FlatIndex::scan_filter passes rows16 only then): both passes stream the image
   if (a.rows16 != nullptr && a.mode == 0 && !exp_variant) {
@@ -1426,6 +1600,20 @@ hipError_t launch_flat_filter(const FlatFilterArgs &a, uint32_t blocks, hipStrea
     fn = a.early ? reinterpret_cast<const void *>(&flat_filter_early_kernel<false, false, false, true>)
                  : reinterpret_cast<const void *>(&flat_filter_bdma_kernel<false, false, false, true>);
     lds = flat_filter_dma_lds_bytes();
+  }
+  // the 16x16x32 consumers (option filter-mfma-shape): the final passes of f32 rows in the inner-product space -- over the image
+  // and, with the B operands by DMA, through registers: the two multiply alike, whichever shape -- and of the bf16 DMA kernel
+  if (a.mfma16 && a.mode == 0 && !exp_variant && !a.l2) {
+    if (a.qbf16 && a.dma) {
+      fn = a.early ? reinterpret_cast<const void *>(&flat_filter_early_bfmma_dma_m16_kernel) : reinterpret_cast<const void *>(&flat_filter_bfmma_dma_m16_kernel);
+    } else if (a.rows16 != nullptr) {
+      fn = a.early ? reinterpret_cast<const void *>(&flat_filter_early_kernel<false, false, false, true, true>)
+                   : reinterpret_cast<const void *>(&flat_filter_bdma_kernel<false, false, false, true, true>);
+    } else if (a.bdma && !a.bf16 && !a.qbf16) {
+      fn = a.early ? reinterpret_cast<const void *>(&flat_filter_early_kernel<false, false, false, false, true>)
+                   : reinterpret_cast<const void *>(&flat_filter_bdma_kernel<false, false, false, false, true>);
+      lds = flat_filter_bdma_lds_bytes(true);
+    }
   }
 #ifdef VK_EXPERIMENTS
   if (a.timing) {

@@ -1042,6 +1042,7 @@ class FlatIndex final : public Index {
     f.qbf16 = (store_.bf16() && !l2() && opt_.get(kOptFilterBf16Mfma) != 0 && !filter_experiment) ? 1 : 0;
     f.dma = (f.qbf16 && opt_.get(kOptFilterRowDma) != 0) ? 1 : 0;
     f.bdma = opt_.get(kOptFilterBDma) != 0 ? 1u : 0u;
+    f.mfma16 = (!l2() && !filter_experiment && opt_.get(kOptFilterMfmaShape) != 0) ? 1u : 0u;   // (read per batch, like bdma: an A/B on one index)
     f.hn16 = l2() ? d_hn16_.as<uint32_t>() : nullptr;
     // the f16 image of f32 rows (ensure_image): read by both passes of mode 0 when it is there and wanted (the option is
     // read per batch: an A/B on one index); held shared until the passes are enqueued, against a release in between

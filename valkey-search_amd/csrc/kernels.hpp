@@ -184,6 +184,10 @@ struct FlatFilterArgs {
   uint32_t row_stride_f, n_rows, nq;
   uint32_t nqt;               // query tiles of 32 (<= 8 per launch)
   const uint32_t *cancel;
+  // final pass, inner-product space: the consumers multiply with v_mfma_f32_16x16x32 instead of 32x32x16 (option
+  // filter-mfma-shape) -- f32 rows over the image or, with bdma, through registers; bf16 rows with qbf16 and dma.  Every other
+  // kernel ignores it.
+  uint32_t mfma16;
 #ifdef VK_EXPERIMENTS
   // the -DVK_EXPERIMENTS build only (csrc/Makefile `experiments`): kernels whose answers are INVALID, for timing
   uint32_t timing;            // VK_FILTER_TIMING=1: the kernel variant with cycle counters per phase (f32 rows, IP only)

@@ -37,7 +37,7 @@ enum OptId : uint32_t {
   kOptKernelTiming,         // 1 = HIP event pairs around the dominant kernel's launches (vk_index_stats.filter_kernel_ns)
   // ---- FLAT: kernel selection and the candidate filter (K4h) ------------------------------------------------------------
   kOptFlatFilter, kOptFilterMinQueries, kOptFilterMinRows, kOptFilterPrepassRows, kOptFilterCap, kOptFilterSpillChunks,
-  kOptFilterBDma, kOptFilterRowDma, kOptFilterBf16Mfma, kOptFlatForceScan, kOptFlatFusedRerank, kOptFilterSecondBound, kOptFilterTwoPass, kOptFilterTwoPassMinTiles, kOptFilterEarlyPermille, kOptFlatF16Image,
+  kOptFilterBDma, kOptFilterRowDma, kOptFilterBf16Mfma, kOptFlatForceScan, kOptFlatFusedRerank, kOptFilterSecondBound, kOptFilterTwoPass, kOptFilterTwoPassMinTiles, kOptFilterEarlyPermille, kOptFlatF16Image, kOptFilterMfmaShape,
   kOptGemmLockstep, kOptGemmPrepassRows, kOptGemmContig, kOptScanMinNrp, kOptUploadParallel,
   // ---- HNSW ----------------------------------------------------------------------------------------------------------------
   kOptHnswStageAdds, kOptHnswStageMax,
@@ -86,6 +86,7 @@ inline const OptDesc &opt_desc(uint32_t id) {
       {"filter-two-pass-min-tiles", "VK_FILTER_TWO_PASS_MIN_TILES", 16, 2, 1u << 20},   // ... for indexes of at least this many 128-row tiles per block (CU)
       {"filter-early-permille", "VK_FILTER_EARLY_PERMILLE", 0, 0, 250},          // ... the early pass's share of the rows (0 = sqrt(sample / rows))
       {"flat-f16-image", "VK_FLAT_F16_IMAGE", 1, 0, 1},                           // f32 rows, IP / COSINE: the filter reads a resident f16 image of the rows (+50 % of the row table)
+      {"filter-mfma-shape", "VK_FILTER_MFMA_SHAPE", 1, 0, 1},                     // final passes in the IP / COSINE space (f32 rows, bf16 rows by DMA): 0 = v_mfma 32x32x16, 1 = 16x16x32
       {"gemm-lockstep", "VK_GEMM_LOCKSTEP", 1, 0, 64},
       {"gemm-prepass-rows", "VK_GEMM_PREPASS", 16384, 0, kMax},
       {"gemm-contig", "VK_GEMM_CONTIG", 1, 0, 1},
