@@ -15,6 +15,7 @@
 // Both kernels: one wave per node, distances 16 rows at a time (one row per quad of lanes) against a
 // "query" row staged in LDS, the same lane-exact f32 arithmetic as everywhere else.
 #include "device_common.hpp"
+#include "hnsw_relink_order.hpp"
 #include "kernels.hpp"
 
 namespace vk {
@@ -105,7 +106,9 @@ __global__ __launch_bounds__(256) void hnsw_relink_kernel(HnswBuildArgs a) {
   extern __shared__ float4 lds4[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int j = lane & 3, rq = lane >> 2;
-  constexpr uint32_t kCap = 256;                            // candidates per node (old list + additions)
+  // candidates per node (old list + additions).  cnt <= max_keep <= 192 < kCap is the caller's guarantee (the host
+  // takes this path only for maxM0 <= 192: hnsw_index.cc add_batch_device and stage_candidate), so kCap - cnt never wraps
+  constexpr uint32_t kCap = 256;
   const size_t per_wave_f4 = (size_t)a.chunks * 4 + (kCap * 4 + a.max_keep + 3) / 4;
   float4 *qs = lds4 + wave * per_wave_f4;
   float *c_d = reinterpret_cast<float *>(qs + a.chunks * 4);
@@ -140,18 +143,12 @@ __global__ __launch_bounds__(256) void hnsw_relink_kernel(HnswBuildArgs a) {
   }
   for (uint32_t i = lane; i < nadd; i += kWave) { c_d[cnt + i] = a.add_d[a0 + i]; c_id[cnt + i] = a.add_p[a0 + i]; }
   const uint32_t total = cnt + nadd;
-  // ascending by (distance, id): rank by counting
+  // ascending by (distance, id, position), NaN distances last: rank by counting.  The order is total
+  // (hnsw_relink_order.hpp), so the ranks are a permutation and every slot of s_d / s_id [0, total) is written
   for (uint32_t i = lane; i < total; i += kWave) {
-    const float di = c_d[i];
-    const uint32_t ii = c_id[i];
-    uint32_t rank = 0;
-    for (uint32_t o = 0; o < total; ++o) {
-      const float dO = c_d[o];
-      const uint32_t io = c_id[o];
-      rank += (dO < di || (dO == di && io < ii)) ? 1u : 0u;
-    }
-    s_d[rank] = di;
-    s_id[rank] = ii;
+    const uint32_t rank = relink_rank(c_d, c_id, total, i);
+    s_d[rank] = c_d[i];
+    s_id[rank] = c_id[i];
   }
   uint32_t nk = 0;
   for (uint32_t ci = 0; ci < total && nk < a.max_keep; ++ci) {
