@@ -509,7 +509,8 @@ int vk_index_shard_commit_device_rows(vk_index *ix, uint32_t shard, uint64_t n_r
  * k smallest by (distance,label) out of `parts` per-shard lists: the role of
  * SearchPartitionResultsTracker::AddResult (fanout.cc:162-175), with the total order of
  * bruteforce.h's heap so that an n-shard answer equals the 1-shard answer.
- * Device pointers; lists laid out [parts][nq][k]; enqueued on hip_stream. */
+ * Device pointers; lists laid out [parts][nq][k]; enqueued on hip_stream.
+ * Precondition: no distance in the lists is NaN (a scan never emits one); empty entries are (+inf, ~0). */
 int vk_merge_topk_device(const float *d_dist, const uint64_t *d_label, uint32_t parts, uint64_t nq,
                          uint64_t k, float *d_out_dist, uint64_t *d_out_label, uint32_t *d_out_n,
                          int device_id, void *hip_stream);
