@@ -429,6 +429,38 @@ class HNSW:
             raise RuntimeError(last_error())
         return self
 
+    @classmethod
+    def from_arrays(cls, rows, labels, l0, upper, max_level, entry_point, space, M, isa="skylake", ef_construction=200,
+                    ef=10):
+        """Oracle index over a graph given as the dense arrays export_graph() returns, adopted WITHOUT validation
+        (vko_hnsw_load_graph): `l0` is [n][2M+1] with word 0 = count | tombstone << 16 (export_graph keeps the tombstones
+        in `deleted`: pass l0 with `l0[:, 0] |= deleted << 16`), `upper` is {(node, level): ids} with every level
+        1 .. levels(node) present.  Lists may repeat an id or name their own node: the search treats them as hnswlib does."""
+        rows = f32(np.atleast_2d(rows))
+        n, dim = rows.shape
+        labels = np.ascontiguousarray(labels, dtype=np.uint64)
+        l0 = np.ascontiguousarray(l0, dtype=np.uint32)
+        assert l0.shape == (n, 2 * M + 1) and labels.shape == (n,)
+        levels = np.zeros(n, np.int64)
+        for (i, lv) in upper:
+            levels[i] = max(levels[i], lv)
+        off = np.zeros(n + 1, np.uint64)
+        off[1:] = np.cumsum(levels * (M + 1))
+        up = np.zeros(max(int(off[n]), 1), np.uint32)
+        for (i, lv), ids in upper.items():
+            ids = np.asarray(ids, dtype=np.uint32)
+            assert 1 <= lv <= levels[i] and ids.size <= M
+            at = int(off[i]) + (lv - 1) * (M + 1)
+            up[at] = ids.size
+            up[at + 1:at + 1 + ids.size] = ids
+        self = cls(dim, space, isa=isa, max_elements=max(n, 1), M=M, ef_construction=ef_construction, ef=ef)
+        rc = LIB.vko_hnsw_load_graph(self._h, n, _fp(rows), labels.ctypes.data_as(_u64p), l0.ctypes.data_as(_u32p),
+                                     off.ctypes.data_as(_u64p), up.ctypes.data_as(_u32p), int(max_level),
+                                     int(entry_point) & 0xFFFFFFFF)
+        if rc:
+            raise RuntimeError(last_error())
+        return self
+
     def export_graph(self):
         """Dense arrays describing the graph (for feeding the device path the same graph)."""
         n = self.count

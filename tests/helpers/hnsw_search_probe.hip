@@ -1,0 +1,341 @@
+// hnsw_search_probe.hip -- TEST INFRASTRUCTURE (tests/test_hnsw_search_kernels_gpu.py), not part of libvkindex.so.
+//
+// The HNSW search (valkey-search_amd/csrc/hnsw_search.hip, K5 + K6: nine __global__ entry points over one body) is reachable
+// through the C ABI only behind hnsw_index.cc, which decides every launch argument and only ever searches graphs our own
+// build or hnswlib produced.  This probe includes that translation unit itself (compile with -I valkey-search_amd/csrc and
+// the library's flags), so the product's kernels and launcher are what runs -- on a graph, a launch description and scratch
+// memory the test chooses.  One call = one launch, or two chained the way HnswIndex chains them (the second reads the
+// first's redo_out as its redo_in and adds to the same stats).  visited, pool_g, the three outputs and the body of redo_out
+// are filled with a 32-bit pattern first; queue, redo_out[0], stats and totals are zeroed, as the product zeroes them.
+//
+// Return codes: 0 = done, 1 = the arguments were refused (the kernels trust their caller; nothing refused is launched),
+// 2 = a launch did not finish within kStopSeconds and had to be cancelled through its cancel word (a finding to explain by
+// reading, not a case to re-run), anything else = the source line that saw a HIP error; nothing is retried.
+#include "hnsw_search.hip"
+
+#include <string.h>
+#include <time.h>
+
+#include <vector>
+
+namespace vk {
+// kernels.hpp: the library's version (filter_set.cc) remembers what it has raised; one call per launch is enough here
+hipError_t ensure_max_lds(const void *fn) { return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }
+}  // namespace vk
+
+extern "C" {
+
+struct HsGraph {
+  const void *rows;             // [n_nodes][row_stride] f32 or bf16 elements (bf16 as the launch says)
+  const uint64_t *labels;       // [n_nodes]
+  const uint32_t *links0;       // [n_nodes][l0_stride]
+  const int32_t *levels;        // [n_nodes] upper levels of each node (what the slot table was sized with)
+  const uint32_t *upper_slot;   // [n_nodes]
+  const uint32_t *upper_pool;   // [n_slots][up_stride]
+  const float *queries;         // [nq][q_stride]
+  uint32_t row_stride, chunks, l0_stride, up_stride, n_slots, entry_point;
+  int32_t max_level;
+  uint32_t n_nodes, q_stride, nq;
+};
+
+struct HsLaunch {
+  int32_t l2, bf16, e;
+  uint32_t ef, k, blocks, cand_cap, gpool_level, vis_hash_log2, vis_mode, nbr_cap, check_deleted, out_ids;
+  uint32_t with_redo_out, with_totals, pattern, cancel;
+  uint64_t allow_nbits;
+  const uint64_t *allow_bits;               // host, (allow_nbits + 63) / 64 words, or null
+  const uint64_t *const *allow_tab;         // host [nq] of host pointers (null entries allowed), or null
+  const uint64_t *allow_nbits_tab;          // host [nq]
+  const uint64_t *live_bits, *mask_bits;    // host, (n_nodes + 63) / 64 words, or null
+  const uint64_t *const *mask_tab;          // host [nq] of host pointers (null entries allowed), or null
+  const uint32_t *cancel_q;                 // host [nq] values for the pinned per-query words, or null
+  // handed back whole
+  float *out_dist;                          // [nq][k]
+  uint64_t *out_label;                      // [nq][k]
+  uint32_t *out_n;                          // [nq]
+  uint64_t *stats;                          // [5]
+  uint64_t *totals;                         // [2]
+  uint32_t *redo;                           // [1 + nq]
+  uint32_t queue, waves_per_block, lds_bytes, latency, blocks_used;
+};
+
+}  // extern "C"
+
+namespace {
+
+constexpr double kStopSeconds = 30.0;   // a stop, not a performance claim: these launches take milliseconds
+
+struct DevBuf {   // freed on every way out
+  void *p = nullptr;
+  size_t bytes = 0;
+  ~DevBuf() { (void)hipFree(p); }
+  hipError_t alloc(size_t b) { bytes = (b + 15) & ~(size_t)15; if (!bytes) bytes = 16; return hipMalloc(&p, bytes); }
+  hipError_t fill(uint32_t pattern) { return hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(p), (int)pattern, bytes / 4); }
+  template <class T> T *as() const { return static_cast<T *>(p); }
+};
+struct PinBuf {
+  void *p = nullptr;
+  ~PinBuf() { (void)hipHostFree(p); }
+  hipError_t alloc(size_t b) { return hipHostMalloc(&p, b ? b : 4, hipHostMallocDefault); }
+  template <class T> T *as() const { return static_cast<T *>(p); }
+};
+
+#define HS_TRY(expr) do { if ((expr) != hipSuccess) return __LINE__; } while (0)
+#define HS_UP(buf, src, b) do { HS_TRY((buf).alloc(b)); if (b) HS_TRY(hipMemcpy((buf).p, src, b, hipMemcpyHostToDevice)); } while (0)
+#define HS_DOWN(dst, buf, b) do { if (b) HS_TRY(hipMemcpy(dst, (buf).p, b, hipMemcpyDeviceToHost)); } while (0)
+
+// every level-0 list: count within the row and within nbr_cap, ids inside the graph; every upper list likewise, and every
+// node a list at level L names has a list at level L itself (the descent moves to it and reads that list next)
+bool graph_ok(const HsGraph &g, uint32_t nbr_cap) {
+  if (g.n_nodes == 0 || g.l0_stride < 2 || g.up_stride < 2 || g.entry_point >= g.n_nodes || g.max_level < 0) return false;
+  if (g.chunks == 0 || g.row_stride % 16 != 0 || g.q_stride % 16 != 0 || g.row_stride < 16 * g.chunks || g.q_stride < 16 * g.chunks) return false;
+  if (g.nq == 0) return false;
+  for (uint32_t r = 0; r < g.n_nodes; ++r) {
+    const uint32_t *ll = g.links0 + (size_t)r * g.l0_stride, cnt = ll[0] & 0xFFFFu;
+    if (cnt > g.l0_stride - 1 || cnt > nbr_cap) return false;
+    for (uint32_t i = 0; i < cnt; ++i)
+      if (ll[1 + i] >= g.n_nodes) return false;
+    const int32_t lv = g.levels[r];
+    if (lv < 0 || lv > g.max_level) return false;
+    if (lv > 0 && ((uint64_t)g.upper_slot[r] + (uint32_t)lv > g.n_slots)) return false;
+  }
+  if (g.levels[g.entry_point] != g.max_level) return false;
+  for (uint32_t r = 0; r < g.n_nodes; ++r)
+    for (int32_t lv = 1; lv <= g.levels[r]; ++lv) {
+      const uint32_t *ul = g.upper_pool + (size_t)(g.upper_slot[r] + (uint32_t)(lv - 1)) * g.up_stride, cnt = ul[0] & 0xFFFFu;
+      if (cnt > g.up_stride - 1) return false;
+      for (uint32_t i = 0; i < cnt; ++i)
+        if (ul[1 + i] >= g.n_nodes || g.levels[ul[1 + i]] < lv) return false;
+    }
+  return true;
+}
+
+// what hnsw_search.hip assumes of one launch and hnsw_index.cc guarantees it (HnswSearchArgs, kernels.hpp)
+bool launch_ok(const HsGraph &g, const HsLaunch &l, bool second) {
+  if (l.k < 1 || l.k > l.ef || l.ef > vk::kHnswMaxEf) return false;
+  if (l.gpool_level > 2 || l.vis_mode > 5 || l.vis_mode == 4) return false;
+  const bool lds_list = l.ef > 1024 || (l.ef > 512 && l.gpool_level != 0);
+  if (l.e != (lds_list ? vk::kHnswLdsList : vk::hnsw_slots_per_lane(l.ef))) return false;
+  if (l.nbr_cap == 0 || l.nbr_cap % 64 != 0) return false;
+  const bool hash = l.vis_hash_log2 != 0;
+  if (!hash && l.vis_mode != 0) return false;
+  if (hash) {
+    if (l.vis_hash_log2 < 4 || l.vis_hash_log2 > 20) return false;
+    if (!l.with_redo_out) return false;                       // a table that fills up makes the probe sequence endless
+    if (l.gpool_level != 0 || second) return false;           // (hnsw_pick returns null)
+    if (l.vis_mode == 2 && l.vis_hash_log2 < 5) return false;
+    if ((l.vis_mode == 3 || l.vis_mode == 5) && g.n_nodes >= (1u << 24)) return false;
+    if (l.vis_mode == 3 && !(l.e >= 1 && l.e <= 16)) return false;
+    if (l.vis_mode == 5 && !(l.e >= 1 && l.e <= 8)) return false;
+  }
+  if (second && l.with_redo_out) return false;                // (the product's second launch has nowhere to abandon to)
+  const bool selective = l.allow_bits || l.allow_tab || l.mask_bits || l.mask_tab || l.live_bits || l.check_deleted;
+  if (l.gpool_level == 0) {
+    if (l.cand_cap == 0) return false;
+    if (!hash && !selective && l.cand_cap < 2 * l.ef) return false;
+  } else if (l.gpool_level == 1) {
+    if (l.cand_cap == 0 || l.cand_cap % 128 != 0 || l.cand_cap > 65536) return false;
+    if (!l.with_redo_out && l.cand_cap < g.n_nodes) return false;
+  } else {
+    if (l.cand_cap == 0 || l.cand_cap % 8192 != 0 || l.cand_cap < g.n_nodes) return false;
+  }
+  if (l.out_ids && (l.live_bits || l.mask_bits || l.mask_tab)) return false;
+  if (l.allow_bits && l.allow_nbits == 0) return false;
+  if (l.allow_tab && !l.allow_nbits_tab) return false;
+  return true;
+}
+
+double now_s() {
+  timespec ts;
+  clock_gettime(CLOCK_MONOTONIC, &ts);
+  return ts.tv_sec + ts.tv_nsec * 1e-9;
+}
+
+// a table of per-query bitmaps: the distinct host pointers are uploaded once each
+struct BitTab {
+  std::vector<DevBuf> bufs;
+  DevBuf tab;
+  int up(const uint64_t *const *host_tab, uint32_t nq, const uint64_t *nbits_tab, uint64_t fixed_words) {
+    std::vector<const uint64_t *> dev(nq, nullptr);
+    bufs.resize(nq);
+    for (uint32_t q = 0; q < nq; ++q) {
+      if (!host_tab[q]) continue;
+      uint32_t p = 0;
+      while (p < q && host_tab[p] != host_tab[q]) ++p;
+      if (p < q && (nbits_tab == nullptr || nbits_tab[p] >= nbits_tab[q])) { dev[q] = dev[p]; continue; }
+      const uint64_t words = nbits_tab ? (nbits_tab[q] + 63) / 64 : fixed_words;
+      HS_UP(bufs[q], host_tab[q], (size_t)words * 8);
+      dev[q] = bufs[q].as<uint64_t>();
+    }
+    HS_UP(tab, dev.data(), (size_t)nq * 8);
+    return 0;
+  }
+};
+
+struct Shared {   // what both launches of a call see
+  DevBuf rows, labels, links, uslot, upool, queries, out_d, out_l, out_n, stats, totals, redo;
+  PinBuf cancel;
+};
+
+int run_one(const HsGraph &g, HsLaunch &l, Shared &sh, bool second) {
+  vk::HnswSearchArgs a{};
+  a.rows = sh.rows.p;
+  a.labels = sh.labels.as<uint64_t>();
+  a.links0 = sh.links.as<uint32_t>();
+  a.upper_slot = sh.uslot.as<uint32_t>();
+  a.upper_pool = sh.upool.as<uint32_t>();
+  a.queries = sh.queries.as<float>();
+  a.out_dist = sh.out_d.as<float>();
+  a.out_label = sh.out_l.as<uint64_t>();
+  a.out_n = sh.out_n.as<uint32_t>();
+  a.stats = sh.stats.as<unsigned long long>();
+  a.queue = reinterpret_cast<uint32_t *>(a.stats + 6) + (second ? 1 : 0);
+  a.totals = l.with_totals ? sh.totals.as<unsigned long long>() : nullptr;
+  a.row_stride_f = g.row_stride;
+  a.q_stride_f = g.q_stride;
+  a.chunks = g.chunks;
+  a.l0_stride = g.l0_stride;
+  a.up_stride = g.up_stride;
+  a.entry_point = g.entry_point;
+  a.max_level = g.max_level;
+  a.n_nodes = g.n_nodes;
+  a.bitmap_words = l.vis_hash_log2 ? 1u << l.vis_hash_log2 : (((g.n_nodes + 31) / 32) + 3) & ~3u;
+  a.nq = g.nq;
+  a.k = l.k;
+  a.ef = l.ef;
+  a.cand_cap = l.cand_cap;
+  a.gpool_level = l.gpool_level;
+  a.vis_hash_log2 = l.vis_hash_log2;
+  a.vis_mode = l.vis_mode;
+  a.nbr_cap = l.nbr_cap;
+  a.check_deleted = l.check_deleted;
+  a.out_ids = l.out_ids;
+  a.redo_out = l.with_redo_out ? sh.redo.as<uint32_t>() : nullptr;
+  a.redo_in = second ? sh.redo.as<uint32_t>() : nullptr;
+  a.pool_g = l.gpool_level ? reinterpret_cast<float *>(8) : nullptr;   // (placeholder until the buffer is sized below)
+
+  // filter and masks
+  const uint64_t mask_words = ((uint64_t)g.n_nodes + 63) / 64;
+  DevBuf allow, live, mask, nbits_tab;
+  BitTab allow_tab, mask_tab;
+  if (l.allow_bits) { HS_UP(allow, l.allow_bits, (size_t)((l.allow_nbits + 63) / 64) * 8); a.allow_bits = allow.as<uint64_t>(); a.allow_nbits = l.allow_nbits; }
+  if (l.allow_tab) {
+    if (int rc = allow_tab.up(l.allow_tab, g.nq, l.allow_nbits_tab, 0)) return rc;
+    HS_UP(nbits_tab, l.allow_nbits_tab, (size_t)g.nq * 8);
+    a.allow_tab = allow_tab.tab.as<const uint64_t *>();
+    a.allow_nbits_tab = nbits_tab.as<uint64_t>();
+  }
+  if (l.live_bits) { HS_UP(live, l.live_bits, (size_t)mask_words * 8); a.live_bits = live.as<uint64_t>(); }
+  if (l.mask_bits) { HS_UP(mask, l.mask_bits, (size_t)mask_words * 8); a.mask_bits = mask.as<uint64_t>(); }
+  if (l.mask_tab) {
+    if (int rc = mask_tab.up(l.mask_tab, g.nq, nullptr, mask_words)) return rc;
+    a.mask_tab = mask_tab.tab.as<const uint64_t *>();
+  }
+  // cancellation words in pinned host memory: [0] the launch's (always passed, as the product does), [1 ..] per query
+  uint32_t *cw = sh.cancel.as<uint32_t>();
+  cw[0] = l.cancel ? 1u : 0u;
+  for (uint32_t q = 0; q < g.nq; ++q) cw[1 + q] = l.cancel_q ? l.cancel_q[q] : 0u;
+  a.cancel = cw;
+  a.cancel_q = l.cancel_q ? cw + 1 : nullptr;
+
+  l.waves_per_block = (uint32_t)vk::hnsw_waves_per_block(a);
+  l.lds_bytes = (uint32_t)vk::hnsw_lds_bytes(a);
+  l.latency = vk::hnsw_uses_latency_variant(a) ? 1u : 0u;
+  if (vk::hnsw_lds_bytes(a) > 160 * 1024) return 1;
+  int max_blocks = 0;
+  if (vk::hnsw_max_blocks(a, l.l2 != 0, l.bf16 != 0, l.e, &max_blocks) != hipSuccess) return 1;
+  // blocks == 0: sized as the product sizes a launch -- what fits the device, at most one wave slot per query
+  const uint32_t wpb = l.waves_per_block;
+  uint32_t blocks = l.blocks ? l.blocks : std::min<uint32_t>((g.nq + wpb - 1) / wpb, (uint32_t)max_blocks);
+  if (blocks > (uint32_t)max_blocks) return 1;
+  l.blocks_used = blocks;
+  const uint64_t slots = (uint64_t)blocks * wpb;
+  const uint64_t pool_per_wave = l.gpool_level == 2 ? (uint64_t)l.cand_cap * 8 + (uint64_t)l.cand_cap / 64 * 4
+                                 : l.gpool_level == 1 ? (uint64_t)l.cand_cap * 8 : 0;
+  if (slots * (uint64_t)a.bitmap_words * 4 > ((uint64_t)1 << 31) || slots * pool_per_wave > ((uint64_t)1 << 31)) return 1;
+
+  DevBuf visited, pool;
+  HS_TRY(visited.alloc((size_t)(slots * a.bitmap_words * 4)));
+  HS_TRY(visited.fill(l.pattern));
+  a.visited = visited.as<uint32_t>();
+  if (l.gpool_level) {
+    HS_TRY(pool.alloc((size_t)(slots * pool_per_wave)));
+    HS_TRY(pool.fill(l.pattern));
+    a.pool_g = pool.as<float>();
+  }
+  if (!second) {   // (the second launch adds to the first's outputs and statistics, like the product's)
+    HS_TRY(sh.out_d.fill(l.pattern));
+    HS_TRY(sh.out_l.fill(l.pattern));
+    HS_TRY(sh.out_n.fill(l.pattern));
+    HS_TRY(sh.redo.fill(l.pattern));
+    HS_TRY(hipMemset(sh.stats.p, 0, 64));
+    HS_TRY(hipMemset(sh.totals.p, 0, 16));
+    if (l.with_redo_out) HS_TRY(hipMemset(sh.redo.p, 0, 4));
+  }
+  HS_TRY(hipDeviceSynchronize());
+
+  hipStream_t s = nullptr;
+  HS_TRY(hipStreamCreate(&s));
+  int rc = 0;
+  if (vk::launch_hnsw_search(a, l.l2 != 0, l.bf16 != 0, l.e, blocks, s) != hipSuccess) rc = __LINE__;
+  if (!rc) {   // no blocking wait: a launch that does not end is stopped through its cancel word
+    const double t0 = now_s();
+    bool raised = false;
+    for (;;) {
+      const hipError_t q = hipStreamQuery(s);
+      if (q == hipSuccess) break;
+      if (q != hipErrorNotReady) { rc = __LINE__; break; }
+      if (!raised && now_s() - t0 > kStopSeconds) {
+        __atomic_store_n(cw, 1u, __ATOMIC_SEQ_CST);
+        raised = true;
+      }
+      timespec nap{0, 200000};
+      nanosleep(&nap, nullptr);
+    }
+    if (!rc && raised) rc = 2;
+  }
+  (void)hipStreamDestroy(s);
+  if (rc) return rc;
+
+  HS_DOWN(l.out_dist, sh.out_d, (size_t)g.nq * l.k * 4);
+  HS_DOWN(l.out_label, sh.out_l, (size_t)g.nq * l.k * 8);
+  HS_DOWN(l.out_n, sh.out_n, (size_t)g.nq * 4);
+  unsigned long long st[8];
+  HS_DOWN(st, sh.stats, 64);
+  for (int i = 0; i < 5; ++i) l.stats[i] = st[i];
+  l.queue = reinterpret_cast<const uint32_t *>(st + 6)[second ? 1 : 0];
+  HS_DOWN(l.totals, sh.totals, 16);
+  HS_DOWN(l.redo, sh.redo, ((size_t)g.nq + 1) * 4);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int hs_probe(const HsGraph *gp, HsLaunch *first, HsLaunch *second) {
+  const HsGraph &g = *gp;
+  if (!first || !graph_ok(g, first->nbr_cap) || !launch_ok(g, *first, false)) return 1;
+  if (second) {
+    // chained as HnswIndex chains them: same element type, metric, k and ef; the first launch must have a redo list
+    if (!graph_ok(g, second->nbr_cap) || !launch_ok(g, *second, true) || !first->with_redo_out) return 1;
+    if (second->k != first->k || second->ef != first->ef || second->bf16 != first->bf16 || second->l2 != first->l2) return 1;
+  }
+  Shared sh;
+  const size_t esz = first->bf16 ? 2 : 4;
+  HS_UP(sh.rows, g.rows, (size_t)g.n_nodes * g.row_stride * esz);
+  HS_UP(sh.labels, g.labels, (size_t)g.n_nodes * 8);
+  HS_UP(sh.links, g.links0, (size_t)g.n_nodes * g.l0_stride * 4);
+  HS_UP(sh.uslot, g.upper_slot, (size_t)g.n_nodes * 4);
+  HS_UP(sh.upool, g.upper_pool, (size_t)g.n_slots * g.up_stride * 4);
+  HS_UP(sh.queries, g.queries, (size_t)g.nq * g.q_stride * 4);
+  HS_TRY(sh.out_d.alloc((size_t)g.nq * first->k * 4));
+  HS_TRY(sh.out_l.alloc((size_t)g.nq * first->k * 8));
+  HS_TRY(sh.out_n.alloc((size_t)g.nq * 4));
+  HS_TRY(sh.stats.alloc(64));
+  HS_TRY(sh.totals.alloc(16));
+  HS_TRY(sh.redo.alloc(((size_t)g.nq + 1) * 4));
+  HS_TRY(sh.cancel.alloc(((size_t)g.nq + 1) * 4));
+  if (int rc = run_one(g, *first, sh, false)) return rc;
+  if (second)
+    if (int rc = run_one(g, *second, sh, true)) return rc;
+  return 0;
+}

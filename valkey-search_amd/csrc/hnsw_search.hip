@@ -296,8 +296,10 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a) {
     // in HBM; how many ids a bucket holds is a byte in LDS.  An id lives in the first bucket from its home bucket on that
     // had room when it came (buckets only fill up, so every bucket in front of it is full for good).  Look-up: the
     // count from LDS -- zero: the id is new and nothing is read -- else ONE 32-B read of the bucket, on to the next
-    // bucket only behind a full one.  Insert: a slot number from an LDS atomic (the lanes of the wave insert the distinct
-    // ids of one list at the same time) and a 4-B store nobody waits for.  Exact like the table of mode 0/1: ids, not
+    // bucket only behind a full one.  Insert: a slot number from an LDS atomic (the lanes of the wave insert ids of one
+    // list at the same time; a list may name an id twice -- nothing makes the ids distinct -- and look-up and insert are
+    // two steps here, so the expansion loop drops the later of two equal ids of a round before it inserts) and a 4-B store
+    // nobody waits for.  Exact like the table of mode 0/1: ids, not
     // fingerprints.  A count can pass kVisBucket only by the lanes that raced for the last slots (< 64): it fits its byte.
     const uint32_t vis_bmask = ((1u << a.vis_hash_log2) / kVisBucket) - 1u;
     const __amdgpu_buffer_rsrc_t vis_rsrc = __builtin_amdgcn_make_buffer_rsrc(bitmap, 0, (int)(a.bitmap_words * 4u), 0x00020000);
@@ -408,8 +410,9 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a) {
         return true;
       } else if constexpr (kHash == 1) {
         // exact set of ids, linear probing from a multiplicative hash; never more than 3/4 full (checked per hop), so
-        // the probe ends.  The lanes of the wave insert the (distinct) ids of one list at the same time: two that meet in
-        // a slot are told apart by the compare-and-swap
+        // the probe ends.  The lanes of the wave insert the ids of one list at the same time: two that meet in a slot are
+        // told apart by the compare-and-swap -- and if the list names one id twice, one lane wins the slot and the other
+        // reads its own id there: "visited", like the second occurrence in the reference
         const uint32_t mask = (1u << a.vis_hash_log2) - 1u;
         uint32_t h = (id * 2654435761u) >> (32u - a.vis_hash_log2);
         for (;;) {
@@ -676,6 +679,18 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a) {
             if (r == 2u) unv = visit_hbm(nid);
             q_hbm += (uint32_t)__popcll(spill);
           }
+        } else if constexpr (kHash == 2) {
+          // every look-up of a round runs before any of its inserts, so an id the list names twice within one round of 64 is
+          // new to both lanes: the later lane yields -- the second occurrence is "visited", the reference's decision
+          // (hnswalg.h:453-464).  (Across rounds the count in LDS and the bucket in memory already say so.)
+          uint32_t vb = 0;
+          if (i < size) { nid = base == 0 ? nid_first : ll[1 + i]; unv = !vis_lookup(nid, vb); }
+          for (uint64_t fm = __ballot(unv); fm; fm &= fm - 1) {
+            const int fl = __ffsll((unsigned long long)fm) - 1;
+            const uint32_t fid = (uint32_t)__builtin_amdgcn_readlane((int)nid, fl);
+            if (unv && lane > fl && nid == fid) unv = false;
+          }
+          if (unv) vis_insert(nid, vb);
         } else {
           if (i < size) { nid = base == 0 ? nid_first : ll[1 + i]; unv = visit(nid); }
         }

@@ -270,6 +270,22 @@ struct GatherArgs {
 };
 
 // K5 + K6: HNSW search, one wave per query (hnsw_search.hip)
+// The kernels trust their caller.  What hnsw_index.cc guarantees them, in one place (tests/helpers/hnsw_search_probe.hip
+// refuses a launch that breaks any of it):
+//   * graph: every list count <= l0_stride - 1 (up_stride - 1) and <= nbr_cap (a multiple of 64), every id < n_nodes,
+//     entry_point < n_nodes with max_level upper lists, and every node a level-L list names has a level-L list itself.
+//     Lists MAY name an id twice or their own node: every visited set answers "visited" for the second occurrence
+//   * 1 <= k <= ef <= kHnswMaxEf; e == hnsw_slots_per_lane(ef), or kHnswLdsList where the list lives in LDS (ef > 1024, or
+//     ef > 512 with gpool_level != 0); hnsw_lds_bytes <= 160 KB
+//   * bitmap_words: a multiple of 4 covering n_nodes for the bitmap, 1 << vis_hash_log2 for a hash set; visited holds that
+//     many words per wave slot (blocks x hnsw_waves_per_block)
+//   * a hash set only with redo_out (a table that fills up would make the probe sequence endless: the query is given up at
+//     3/4), only with gpool_level == 0 and without redo_in; vis_hash_log2 >= 5 for vis_mode 2; n_nodes < 2^24 for modes 3, 5
+//   * gpool_level 1: cand_cap a multiple of 128, at most 65536, with redo_out unless cand_cap >= n_nodes; gpool_level 2:
+//     cand_cap a multiple of 8192 and >= n_nodes; pool_g sized per wave slot as described at the field
+//   * gpool_level 0 without a hash set: cand_cap >= 2 * ef when there is neither filter, mask nor tombstone; with one, entries
+//     that find the frontier full after the prune are dropped and counted in stats[2] (the host turns that into an error)
+//   * queue, redo_out[0] and (per search) stats zeroed before the launch; cancel / cancel_q in host-pinned memory
 struct HnswSearchArgs {
   const void *rows;            // [cap][row_stride_f] f32 or bf16 elements
   const uint64_t *labels;      // [cap]
