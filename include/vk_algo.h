@@ -114,6 +114,12 @@ class Algo {
       for (uint64_t i = 0; i < n[q]; ++i) out[q].emplace((dist_t)d[q * k + i], (labeltype)l[q * k + i]);
     return out;
   }
+  // ... submitted (vk_index_search_labels_submit; coalescing on): the request is queued and `done(user, status)` fires once the
+  // caller's buffers (k entries each) hold what searchLabels returns; `labels` and the buffers stay valid until then
+  void submitLabels(const void *query, size_t k, const uint64_t *labels, size_t n_labels, float *out_dist, uint64_t *out_label, uint64_t *out_n,
+                    vk_search_done_fn done, void *user) const {
+    Check(vk_index_search_labels_submit(ix_, query, k, labels, n_labels, out_dist, out_label, out_n, done, user));
+  }
   // fstdistfunc_(query, getDataByLabel(label)) as ComputeDistanceFromRecordImpl uses it
   dist_t distance(labeltype label, const void *query) const {
     float d = 0;

@@ -317,6 +317,17 @@ typedef struct vk_prefilter_stats {
   uint64_t fallback_queries;   /* queries answered by the per-query path */
   uint64_t candidate_cap;      /* entries per query the hand-back holds for the most recent batch's k (0: k not covered) */
 } vk_prefilter_stats;
+/* The struct as it has grown at its end (option prefilter-device-resolve).  vk_index_prefilter_stats reads struct_size: a
+ * caller that sets sizeof(vk_prefilter_stats) gets the fields above and nothing is written past them; a caller that sets
+ * sizeof(vk_prefilter_stats_v2) and passes the struct through a cast gets all of them.  On a sharded index the three new
+ * fields are the sums of the shards' own (one label map per shard). */
+typedef struct vk_prefilter_stats_v2 {
+  uint64_t struct_size;
+  uint64_t batches, queries, keys, candidates, fallback_queries, candidate_cap;   /* as in vk_prefilter_stats */
+  uint64_t device_resolved_keys;   /* keys turned into row slots by the device label map (a shared list counts once per batch) */
+  uint64_t label_map_builds;       /* builds of the label map so far (one per publication that a pre-filter batch met) */
+  uint64_t label_map_bytes;        /* device memory the label map holds now (counted in vk_index_stats.device_bytes) */
+} vk_prefilter_stats_v2;
 int vk_index_prefilter_stats(vk_index *ix, vk_prefilter_stats *out);
 /* fstdistfunc_(query, stored row) for one record
  * (ComputeDistanceFromRecordImpl: vector_flat.cc:256-271, vector_hnsw.cc:369-383) */
@@ -354,6 +365,18 @@ int vk_index_search_submit(vk_index *ix, const void *query, uint64_t k, uint64_t
                            const volatile int *cancel_flag, int partial_ok,
                            float *out_dist, uint64_t *out_label, uint64_t *out_n,
                            vk_search_done_fn done, void *user);
+/* vk_index_search_labels, submitted: the pre-filter request of one FT.SEARCH (exact kNN over labels[0 .. n_labels)) queued
+ * with the contract of vk_index_search_submit -- the query is copied, `labels` and the outputs must stay valid until
+ * completion, `done` fires exactly once (or the request is told through the bulk hook when one is set), VK_ERR_BUSY when the
+ * queue is full, VK_ERR_INVALID with coalescing off.  There is no cancellation flag: the blocking call has none.  Such
+ * requests travel in lanes of their own kind, keyed by k; a runner forms a batch under the window rules of the other lanes
+ * and answers it with ONE vk_index_search_labels_batch -- over a shared list when every member brought the same (pointer,
+ * length), over a CSR of the members' lists otherwise.  Each answer is bit for bit what vk_index_search_labels returns for
+ * the request alone.  submitted, rejected, coalesced_batches, coalesced_queries and the latency histogram count these
+ * requests as they count the others. */
+int vk_index_search_labels_submit(vk_index *ix, const void *query, uint64_t k, const uint64_t *labels, uint64_t n_labels,
+                                  float *out_dist, uint64_t *out_label, uint64_t *out_n,
+                                  vk_search_done_fn done, void *user);
 /* Completions told in bulk.  The reference's completion (search.cc:905-908) runs once per FT.SEARCH and re-posts to the main
  * thread; at half a million HNSW queries per second per GPU that per-request hand-over -- a callback, a queue operation and a
  * wake each -- is what bounds the serving rate (r05: 7 us per callback on four completer threads).  With a hook set, the
@@ -452,7 +475,11 @@ int vk_index_search_batch_filter_handles(vk_index *ix, const void *queries, uint
  * prefiltering-threshold-ratio).  Names (csrc/options.hpp has the table with defaults and ranges), e.g.
  *   coalesce-max-batch, coalesce-max-wait-us, max-query-queue-depth, batches-in-flight, shard-ef-pct, shard-gather,
  *   kernel-timing, flat-filter, filter-spill-chunks, hnsw-visited-bytes, hnsw-pool-bytes, hnsw-node-mask (0 / 1; 0 releases
- *   the masks), hnsw-node-mask-bytes, ...
+ *   the masks), hnsw-node-mask-bytes, prefilter-device-resolve (0 / 1, read per batch, ships 0: vk_index_search_labels_batch
+ *   turns labels into row slots with a label map kept on the device -- built on first use, rebuilt whole after a flush that
+ *   published a label, a count or a tombstone, released by vk_index_resize and by the value 0 -- instead of one host hash
+ *   lookup per key; same answers, and a map that finds no room -- on the device, or within prefilter-label-map-bytes, 1 GiB --
+ *   leaves the batch on the host's lookups), ...
  * A sharded index applies an option to itself and to every shard.  Unknown name or value out of range: VK_ERR_INVALID.
  * Options take effect for searches that START after the call; no search path reads the environment. */
 int vk_index_set_option(vk_index *ix, const char *name, uint64_t value);

@@ -74,6 +74,11 @@ class PrefilterStats(C.Structure):
                 ("candidates", C.c_uint64), ("fallback_queries", C.c_uint64), ("candidate_cap", C.c_uint64)]
 
 
+class PrefilterStatsV2(PrefilterStats):
+    """vk_prefilter_stats_v2: vk_prefilter_stats grown at its end (option prefilter-device-resolve)"""
+    _fields_ = [("device_resolved_keys", C.c_uint64), ("label_map_builds", C.c_uint64), ("label_map_bytes", C.c_uint64)]
+
+
 class FilterDelta(C.Structure):
     """vk_filter_delta"""
     _fields_ = [("base", C.c_void_p), ("nbits", C.c_uint64), ("clear_labels", C.c_void_p), ("n_clear", C.c_uint64),
@@ -138,6 +143,7 @@ def lib() -> C.CDLL:
     L.vk_index_set_option.argtypes = [vp, C.c_char_p, u64]
     L.vk_index_get_option.argtypes = [vp, C.c_char_p, u64p]
     L.vk_index_search_submit.argtypes = [vp, vp, u64, u64, vp, u64, vp, i32, vp, vp, vp, SEARCH_DONE, vp]
+    L.vk_index_search_labels_submit.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, SEARCH_DONE, vp]
     L.vk_index_shard_stats.argtypes = [vp, u32, C.POINTER(Stats)]
     L.vk_index_filter_image_bytes.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.vk_index_node_mask_stats.argtypes = [vp, C.POINTER(NodeMaskStats)]
@@ -319,6 +325,27 @@ class Index:
         _PENDING.add(h)
         rc = lib().vk_index_search_submit(self._h, q.ctypes.data, int(k), int(ef), ap, nb, cflag, int(partial_ok), h.d.ctypes.data,
                                           h.l.ctypes.data, h.n.ctypes.data, h.cb, None)
+        if rc != VK_OK:
+            _PENDING.discard(h)
+            _check(rc)
+        return h
+
+    def submit_labels(self, q, k, labels, done):
+        """vk_index_search_labels_submit: search_labels as a queued request.  `labels` (a uint64 array) is used where it lies:
+        requests that bring the SAME array travel over one shared list.  Returns a handle like submit's."""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1)
+        assert labels.dtype == np.uint64 and labels.flags.c_contiguous
+        h = _Pending(q, k, labels, None)
+
+        def _cb(_user, status, h=h, done=done):
+            h.status = status
+            done(status)
+            _PENDING.discard(h)
+
+        h.cb = SEARCH_DONE(_cb)
+        _PENDING.add(h)
+        rc = lib().vk_index_search_labels_submit(self._h, q.ctypes.data, int(k), labels.ctypes.data if labels.size else None, labels.size,
+                                                 h.d.ctypes.data, h.l.ctypes.data, h.n.ctypes.data, h.cb, None)
         if rc != VK_OK:
             _PENDING.discard(h)
             _check(rc)
@@ -540,9 +567,9 @@ class Index:
 
     def prefilter_stats(self) -> PrefilterStats:
         """the counters of search_labels_batch (vk_index_prefilter_stats; a sharded index sums its shards)"""
-        s = PrefilterStats()
-        s.struct_size = C.sizeof(PrefilterStats)
-        _check(lib().vk_index_prefilter_stats(self._h, C.byref(s)))
+        s = PrefilterStatsV2()   # (the struct as it has grown: the fields of PrefilterStats, then the label map's)
+        s.struct_size = C.sizeof(PrefilterStatsV2)
+        _check(lib().vk_index_prefilter_stats(self._h, C.cast(C.byref(s), C.POINTER(PrefilterStats))))
         return s
 
     def distance(self, label, q):

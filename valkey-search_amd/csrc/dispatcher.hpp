@@ -177,6 +177,29 @@ class Dispatcher {
     return enqueue(r, /*bounded=*/true);
   }
 
+  // vk_index_search_labels_submit: one pre-filter request (exact kNN over the caller's key list) queued like a search.  Such
+  // requests travel in lanes of their own kind, keyed by k; a runner hands a batch of them to Index::search_labels_batch --
+  // with ONE shared list when every member brought the same (pointer, length), else with a CSR built from the members'
+  // lists.  The query is copied; `labels` and the outputs stay the caller's until `done`.  No token: the blocking call has none.
+  // (The batch call is handed in by whoever owns the index -- vk_index.cc: Index::search_labels_batch -- so that this header
+  //  needs nothing beyond Index's virtuals at link time: the CPU harnesses build it against a fake index alone.)
+  using LabelsBatchFn = Status (*)(Index *ix, const float *queries, uint64_t nq, uint64_t k, const uint64_t *labels, const uint64_t *list_begin,
+                                   uint64_t n_labels, float *out_dist, uint64_t *out_label, uint64_t *out_n);
+  void set_labels_batch(LabelsBatchFn fn) { labels_fn_ = fn; }
+  Status submit_labels(const float *query, uint64_t k, const uint64_t *labels, uint64_t n_labels, float *out_dist, uint64_t *out_label,
+                       uint64_t *out_n, SearchDoneFn done, void *user) {
+    if (!labels_fn_) return Status::Err(VK_ERR_INVALID, "this dispatcher serves no pre-filter requests");
+    auto r = std::make_shared<Req>();
+    fill(*r, query, k, 0, nullptr, 0, nullptr, nullptr, true, out_dist, out_label, out_n);
+    r->key = Key{k, kLabelsLaneEf, kLabelsLaneFid};
+    r->by_labels = true;
+    r->labels = labels;
+    r->n_labels = n_labels;
+    r->cb = done;
+    r->user = user;
+    return enqueue(r, /*bounded=*/true);
+  }
+
   // vk_index_search with coalescing on: the same queue, the caller waits for its answer -- or for its token.
   Status search(const float *query, uint64_t k, uint64_t ef, const uint64_t *allow_bits, uint64_t allow_nbits,
                 const std::shared_ptr<FilterSet> &filter, const volatile int *cancel_flag, bool partial_ok, float *out_dist,
@@ -263,8 +286,14 @@ class Dispatcher {
     uint64_t k, ef, fid;
     bool operator<(const Key &o) const { return k != o.k ? k < o.k : (ef != o.ef ? ef < o.ef : fid < o.fid); }
   };
+  // the lanes of pre-filter requests: an ef no search carries, a filter id neither a FilterSet (a small counter) nor a bitmap's
+  // address (bit 63) takes
+  static constexpr uint64_t kLabelsLaneEf = ~0ull, kLabelsLaneFid = 1ull << 62;
   struct Req {
     std::vector<float> q;                 // the query, owned by the request
+    bool by_labels = false;               // a pre-filter request (submit_labels): exact kNN over labels[0 .. n_labels)
+    const uint64_t *labels = nullptr;     // ... the caller's memory until the request is answered
+    uint64_t n_labels = 0;
     const uint64_t *allow = nullptr;      // raw host bitmap (the caller's memory: `pinned`)
     uint64_t allow_nbits = 0;
     std::shared_ptr<FilterSet> filter;    // ... or a device-resident filter, kept alive by the request
@@ -494,6 +523,8 @@ class Dispatcher {
     std::vector<const float *> qtab;
     std::vector<const uint64_t *> atab;
     std::vector<const FilterSet *> ftab;
+    std::vector<float> Q;                 // pre-filter batches: the members' queries side by side ...
+    std::vector<uint64_t> keys, begin;    // ... and, unless they share one list, their lists as a CSR
   };
 
   static constexpr uint64_t kOffloadMin = 32;   // (a couple of callbacks are not worth a thread hand-over)
@@ -549,6 +580,32 @@ class Dispatcher {
     return ix_->search(rq, sc.D.data() + first * k, sc.L.data() + first * k, sc.N.data() + first);
   }
 
+  // a batch of pre-filter requests: one Index::search_labels_batch
+  Status search_label_members(uint64_t k, const std::vector<std::shared_ptr<Req>> &batch, Scratch &sc) {
+    const size_t nq = batch.size();
+    sc.Q.resize(nq * dim_);
+    bool shared = true;
+    uint64_t total = 0;
+    for (size_t i = 0; i < nq; ++i) {
+      const Req &r = *batch[i];
+      memcpy(sc.Q.data() + i * dim_, r.q.data(), (size_t)dim_ * 4);
+      shared = shared && r.labels == batch[0]->labels && r.n_labels == batch[0]->n_labels;
+      total += r.n_labels;
+    }
+    if (shared)
+      return labels_fn_(ix_, sc.Q.data(), nq, k, batch[0]->labels, nullptr, batch[0]->n_labels, sc.D.data(), sc.L.data(), sc.N.data());
+    sc.keys.resize(total);
+    sc.begin.resize(nq + 1);
+    uint64_t at = 0;
+    for (size_t i = 0; i < nq; ++i) {
+      sc.begin[i] = at;
+      if (batch[i]->n_labels) memcpy(sc.keys.data() + at, batch[i]->labels, batch[i]->n_labels * 8);
+      at += batch[i]->n_labels;
+    }
+    sc.begin[nq] = at;
+    return labels_fn_(ix_, sc.Q.data(), nq, k, sc.keys.data(), sc.begin.data(), total, sc.D.data(), sc.L.data(), sc.N.data());
+  }
+
   void run_batch(uint64_t k, uint64_t ef, std::vector<std::shared_ptr<Req>> &batch, Scratch &sc) {
     const bool hnsw = ix_->params().algo == VK_ALGO_HNSW;
     // requests whose token is already up are answered without a search
@@ -595,8 +652,9 @@ class Dispatcher {
         w->hnsw = hnsw;
         watch(w);
       }
-      st = search_members(k, ef, batch, 0, nq, sc, w ? &w->word : nullptr, w ? w->words.data() : nullptr);
-      if (!st.ok() && st.code == VK_ERR_INVALID && nq > 1) {
+      if (batch[0]->by_labels) st = search_label_members(k, batch, sc);
+      else st = search_members(k, ef, batch, 0, nq, sc, w ? &w->word : nullptr, w ? w->words.data() : nullptr);
+      if (!batch[0]->by_labels && !st.ok() && st.code == VK_ERR_INVALID && nq > 1) {
         // an argument error may be ONE member's (a filter built for another index, ...): the members are tried alone so
         // that it fails alone
         each.resize(nq);
@@ -776,6 +834,7 @@ class Dispatcher {
   bool stop_flag() const { return stop_watch_.load(std::memory_order_relaxed); }
 
   Index *ix_;
+  LabelsBatchFn labels_fn_ = nullptr;   // set once, before requests are submitted
   const bool flat_;
   const uint32_t dim_;
   std::mutex mu_;

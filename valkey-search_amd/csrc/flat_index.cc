@@ -325,7 +325,29 @@ class FlatIndex final : public Index {
   Status resize(uint64_t new_max) override {
     std::unique_lock<std::shared_mutex> lk(rw_);
     capacity_ = new_max;
+    (void)hipSetDevice(store_.device());
+    label_map_.release();   // (the next pre-filter batch that wants it builds it again)
     return Status::Ok();
+  }
+
+  // prefilter-device-resolve = 0 releases the label map
+  Status set_option(const char *name, uint64_t value) override {
+    VK_TRY(opt_.set(name, value));
+    if (opt_.get(kOptPrefilterDeviceResolve) == 0 && label_map_.bytes() != 0) {
+      std::unique_lock<std::shared_mutex> lk(rw_);
+      (void)hipSetDevice(store_.device());
+      label_map_.release();
+    }
+    return Status::Ok();
+  }
+  void release_label_map() override {
+    std::unique_lock<std::shared_mutex> lk(rw_);
+    (void)hipSetDevice(store_.device());
+    label_map_.release();
+  }
+  void label_map_counters(uint64_t *builds, uint64_t *bytes) override {
+    *builds = label_map_.builds();
+    *bytes = label_map_.bytes();
   }
 
   Status set_ef(uint32_t) override { return Status::Ok(); }
@@ -484,14 +506,28 @@ class FlatIndex final : public Index {
     std::shared_lock<std::shared_mutex> lk(rw_);
     (void)hipSetDevice(store_.device());
     CtxLease lease(pool_);
-    PrefilterResolved r;   // label -> slot once per distinct list
-    prefilter_resolve(labels, list_begin, n_labels, nq, [&](uint64_t label, uint32_t *slot) {
-      auto it = slot_of_.find(label);
-      if (it == slot_of_.end()) return false;
-      *slot = it->second;
-      return true;
-    }, &r);
-    VK_TRY(prefilter_device_stage(lease.ctx, store_.d_rows(), params_.dim, store_.stride_f(), l2(), store_.bf16(), queries, k, r, out));
+    // label -> slot: on the device by the label map (option prefilter-device-resolve) when it is there for this publication
+    // and nothing is staged behind it, on the host otherwise
+    bool on_device = false;
+    LabelMapTable map;
+    if (opt_.get(kOptPrefilterDeviceResolve) != 0 && !store_.dirty() && count_ <= store_.alloc_rows() &&
+        label_map_.ready(store_.label_epoch(), (uint32_t)count_, store_.d_labels(), nullptr, 0, opt_.get(kOptPrefilterLabelMapBytes),
+                         lease.ctx->stream, &map)) {
+      uint64_t resolved = 0;
+      VK_TRY(prefilter_device_stage_keys(lease.ctx, map, store_.d_rows(), params_.dim, store_.stride_f(), l2(), store_.bf16(), queries, nq, k,
+                                         labels, list_begin, n_labels, out, &on_device, &resolved));
+      pf_.device_resolved_keys.fetch_add(resolved, std::memory_order_relaxed);
+    }
+    if (!on_device) {
+      PrefilterResolved r;   // label -> slot once per distinct list
+      prefilter_resolve(labels, list_begin, n_labels, nq, [&](uint64_t label, uint32_t *slot) {
+        auto it = slot_of_.find(label);
+        if (it == slot_of_.end()) return false;
+        *slot = it->second;
+        return true;
+      }, &r);
+      VK_TRY(prefilter_device_stage(lease.ctx, store_.d_rows(), params_.dim, store_.stride_f(), l2(), store_.bf16(), queries, k, r, out));
+    }
     uint64_t cands = 0;
     for (uint64_t q = 0; q < nq; ++q)
       if (!out->fallback[q]) cands += out->begin[q + 1] - out->begin[q];
@@ -534,7 +570,7 @@ class FlatIndex final : public Index {
     memset(out, 0, sizeof(*out));
     out->count = count_;
     out->capacity = capacity_;
-    out->device_bytes = store_.device_bytes() + image_bytes_.load(std::memory_order_relaxed);
+    out->device_bytes = store_.device_bytes() + image_bytes_.load(std::memory_order_relaxed) + label_map_.bytes();
     out->host_bytes = store_.host_bytes() + slot_of_.size() * 24;
     out->staged_ops = store_.staged_ops();
     out->max_level = -1;
@@ -1326,6 +1362,7 @@ class FlatIndex final : public Index {
   OptRef force_scan_{&opt_, kOptFlatForceScan};   // A/B switch for benchmarks: VALU scan for every batch size
   std::unordered_map<uint64_t, uint32_t> slot_of_;  // dict_external_to_internal
   uint64_t count_ = 0;                               // cur_element_count_
+  DeviceLabelMap label_map_;                         // label -> row slot on the device (option prefilter-device-resolve)
   uint64_t capacity_;                                // data_->getCapacity()
 };
 

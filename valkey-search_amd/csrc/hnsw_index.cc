@@ -340,6 +340,8 @@ class HnswIndex final : public Index {
 
   Status resize(uint64_t new_max) override {
     std::unique_lock<std::shared_mutex> lk(rw_);
+    (void)hipSetDevice(store_.device());
+    label_map_.release();   // (the next pre-filter batch that wants it builds it again)
     return graph_->resize(new_max);
   }
 
@@ -524,12 +526,29 @@ class HnswIndex final : public Index {
     std::shared_lock<std::shared_mutex> lk(rw_);
     (void)hipSetDevice(store_.device());
     CtxLease lease(pool_);
-    PrefilterResolved r;   // label -> slot once per distinct list
-    prefilter_resolve(labels, list_begin, n_labels, nq, [&](uint64_t label, uint32_t *slot) {
-      // tombstoned labels are "not found" (vector_hnsw.cc:55-64); so are labels not published to the device yet
-      return graph_->lookup(label, slot) && *slot < pub_.count && !graph_->is_deleted(*slot);
-    }, &r);
-    VK_TRY(prefilter_device_stage(lease.ctx, store_.d_rows(), params_.dim, store_.stride_f(), l2(), store_.bf16(), queries, k, r, out));
+    // label -> internal id: on the device by the label map (option prefilter-device-resolve) when it is there for this
+    // publication and the host graph holds nothing the device has not seen, on the host otherwise.  The map is built from what
+    // the search kernels read -- the published labels and the tombstone bit of each node's level-0 word -- so it knows the
+    // labels the lookup below accepts.
+    bool on_device = false;
+    LabelMapTable map;
+    if (opt_.get(kOptPrefilterDeviceResolve) != 0 && !store_.dirty() && !graph_->any_dirty() && !links_stale_ &&
+        pub_.count <= store_.alloc_rows() &&
+        label_map_.ready(mask_epoch_, pub_.count, store_.d_labels(), pub_.count ? d_links0_.as<uint32_t>() : nullptr,
+                         (uint32_t)graph_->maxM0() + 1, opt_.get(kOptPrefilterLabelMapBytes), lease.ctx->stream, &map)) {
+      uint64_t resolved = 0;
+      VK_TRY(prefilter_device_stage_keys(lease.ctx, map, store_.d_rows(), params_.dim, store_.stride_f(), l2(), store_.bf16(), queries, nq, k,
+                                         labels, list_begin, n_labels, out, &on_device, &resolved));
+      pf_.device_resolved_keys.fetch_add(resolved, std::memory_order_relaxed);
+    }
+    if (!on_device) {
+      PrefilterResolved r;   // label -> slot once per distinct list
+      prefilter_resolve(labels, list_begin, n_labels, nq, [&](uint64_t label, uint32_t *slot) {
+        // tombstoned labels are "not found" (vector_hnsw.cc:55-64); so are labels not published to the device yet
+        return graph_->lookup(label, slot) && *slot < pub_.count && !graph_->is_deleted(*slot);
+      }, &r);
+      VK_TRY(prefilter_device_stage(lease.ctx, store_.d_rows(), params_.dim, store_.stride_f(), l2(), store_.bf16(), queries, k, r, out));
+    }
     uint64_t cands = 0;
     for (uint64_t q = 0; q < nq; ++q)
       if (!out->fallback[q]) cands += out->begin[q + 1] - out->begin[q];
@@ -596,7 +615,8 @@ class HnswIndex final : public Index {
     out->staged_adds = staged_adds_.load(std::memory_order_relaxed);
     out->staged_adds_device = staged_adds_device_.load(std::memory_order_relaxed);
     out->capacity = graph_->max_elements();
-    out->device_bytes = store_.device_bytes() + d_links0_.cap + d_upper_slot_.cap + d_upper_pool_.cap + d_live_.cap + masks_.counters().bytes;
+    out->device_bytes = store_.device_bytes() + d_links0_.cap + d_upper_slot_.cap + d_upper_pool_.cap + d_live_.cap + masks_.counters().bytes +
+                        label_map_.bytes();
     out->host_bytes = store_.host_bytes() + graph_->host_bytes();
     out->staged_ops = store_.staged_ops() + staged;
     out->max_level = graph_->max_level();
@@ -632,7 +652,21 @@ class HnswIndex final : public Index {
       (void)hipSetDevice(store_.device());
       masks_.clear();
     }
+    if (opt_.get(kOptPrefilterDeviceResolve) == 0 && label_map_.bytes() != 0) {   // ... and the label map
+      std::unique_lock<std::shared_mutex> lk(rw_);
+      (void)hipSetDevice(store_.device());
+      label_map_.release();
+    }
     return Status::Ok();
+  }
+  void release_label_map() override {
+    std::unique_lock<std::shared_mutex> lk(rw_);
+    (void)hipSetDevice(store_.device());
+    label_map_.release();
+  }
+  void label_map_counters(uint64_t *builds, uint64_t *bytes) override {
+    *builds = label_map_.builds();
+    *bytes = label_map_.bytes();
   }
 
   Status node_mask_stats(vk_node_mask_stats *out) override {
@@ -1577,6 +1611,7 @@ class HnswIndex final : public Index {
   std::vector<uint64_t> live_host_;
   uint32_t live_count_ = 0;
   uint64_t seen_reuses_ = 0, mask_epoch_ = 1;
+  DeviceLabelMap label_map_;   // label -> internal id on the device (option prefilter-device-resolve), tagged with mask_epoch_
   NodeMaskCache masks_{&HnswIndex::free_mask, this};
   std::atomic<uint64_t> last_mask_served_{0};
   static thread_local const uint64_t *mask_one_;

@@ -109,6 +109,16 @@ int vsa_search_prefiltered(void *p, const void *q, uint64_t qlen, uint64_t k, co
   return emit(static_cast<Handle *>(p)->base->SearchPrefiltered(std::string_view((const char *)q, qlen), k, ks), keys, keys_cap, dist, n);
 }
 
+// ... as a submitted request (vk_index_search_labels_submit; max_batch > 1 switches the index's coalescing on first)
+int vsa_search_prefiltered_submit(void *p, const void *q, uint64_t qlen, uint64_t k, const char *key_list, int64_t n_keys,
+                                  char *keys, uint64_t keys_cap, float *dist, uint64_t *n) {
+  std::vector<std::string> ks;
+  const char *c = key_list;
+  for (int64_t i = 0; i < n_keys; ++i) { ks.emplace_back(c); c += strlen(c) + 1; }
+  return emit(static_cast<Handle *>(p)->base->SearchPrefilteredSubmitted(std::string_view((const char *)q, qlen), k, ks), keys, keys_cap, dist, n);
+}
+void vsa_set_coalescing(void *p, uint32_t max_batch, uint32_t max_wait_us) { static_cast<Handle *>(p)->base->SetCoalescing(max_batch, max_wait_us); }
+
 int vsa_get_value(void *p, const char *key, void *out, uint64_t cap) {
   auto r = static_cast<Handle *>(p)->base->GetValue(key);
   if (!r.ok()) return code_of(r.status());

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <condition_variable>
 
 namespace vsa {
 
@@ -237,6 +238,41 @@ StatusOr<std::vector<Neighbor>> VectorBase::SearchPrefiltered(std::string_view q
   uint64_t n = 0;
   int rc = vk_index_search_labels(ix_, query.data(), count, ids.data(), ids.size(), dist.data(), labels.data(), &n);
   if (rc != VK_OK) return FromVk(rc);
+  return CreateReply(dist.data(), labels.data(), n);
+}
+
+StatusOr<std::vector<Neighbor>> VectorBase::SearchPrefilteredSubmitted(std::string_view query, uint64_t count,
+                                                                       const std::vector<std::string> &keys) const {
+  std::vector<char> norm;
+  if (normalize_) {   // search.cc:463-468
+    norm = NormalizeEmbedding(query, sizeof(float));
+    query = std::string_view(norm.data(), norm.size());
+  }
+  std::shared_lock<std::shared_mutex> lk(key_to_metadata_mutex_);
+  std::vector<uint64_t> ids;
+  ids.reserve(keys.size());
+  for (const auto &k : keys) {
+    auto it = tracked_metadata_by_key_.find(k);
+    if (it != tracked_metadata_by_key_.end()) ids.push_back(it->second.internal_id);
+  }
+  std::vector<float> dist(count ? count : 1);
+  std::vector<uint64_t> labels(count ? count : 1);
+  uint64_t n = 0;
+  struct Wait { std::mutex mu; std::condition_variable cv; bool done = false; int status = 0; } w;
+  int rc = vk_index_search_labels_submit(ix_, query.data(), count, ids.data(), ids.size(), dist.data(), labels.data(), &n,
+                                         [](void *user, int status) {
+                                           Wait *p = static_cast<Wait *>(user);
+                                           std::lock_guard<std::mutex> g(p->mu);
+                                           p->status = status;
+                                           p->done = true;
+                                           p->cv.notify_one();
+                                         }, &w);
+  if (rc != VK_OK) return FromVk(rc);
+  {
+    std::unique_lock<std::mutex> g(w.mu);
+    w.cv.wait(g, [&] { return w.done; });
+  }
+  if (w.status != VK_OK) return FromVk(w.status);
   return CreateReply(dist.data(), labels.data(), n);
 }
 

@@ -110,6 +110,10 @@ class VectorBase {
   StatusOr<std::pair<float, uint64_t>> ComputeDistanceFromRecord(const std::string &key, std::string_view query) const;  // :502-507
   // exact kNN over a key list with the AddPrefilteredKey heap rule (:509-530), device distances
   StatusOr<std::vector<Neighbor>> SearchPrefiltered(std::string_view query, uint64_t count, const std::vector<std::string> &keys) const;
+  // ... through vk_index_search_labels_submit (coalescing on): the request travels in a batch with whatever other readers
+  // submit meanwhile; this call waits for its completion.  Same reply as SearchPrefiltered.
+  StatusOr<std::vector<Neighbor>> SearchPrefilteredSubmitted(std::string_view query, uint64_t count, const std::vector<std::string> &keys) const;
+  void SetCoalescing(uint32_t max_batch, uint32_t max_wait_us) const { (void)vk_index_set_coalescing(ix_, max_batch, max_wait_us); }
   uint64_t GetMaxInternalLabel() const { return inc_id_ ? inc_id_ - 1 : 0; }
   Status SaveIndex(vk_write_chunk_fn fn, void *user) const;
 

@@ -41,6 +41,33 @@ struct PinBuf {
   template <class T> T *as() { return reinterpret_cast<T *>(p); }
 };
 
+// The device label map of one index on one device (label_map.hip; option prefilter-device-resolve): label -> slot for the
+// batched pre-filter search.  Built whole, lazily, on the stream of the first batch that wants it, and tagged with what it was
+// built from: the index's publication counter and published count.  A batch that finds another tag rebuilds it -- a flush
+// stands between the two, and a flush holds the index's lock exclusively, so no kernel of an earlier batch still reads the
+// table.  Callers hold the index's shared lock (ready) or its exclusive lock (release).
+class DeviceLabelMap {
+ public:
+  ~DeviceLabelMap() { buf_.release(); }
+  // false = no map for this publication (no room on the device, or the build's failure word was not zero): the batch
+  // resolves on the host.  links0 != nullptr: HNSW, tombstoned nodes stay out.
+  // budget: most bytes the table may take (option prefilter-label-map-bytes); read when the map is (re)built
+  bool ready(uint64_t epoch, uint32_t count, const uint64_t *d_labels, const uint32_t *d_links0, uint32_t l0_stride, uint64_t budget,
+             hipStream_t s, LabelMapTable *out);
+  void release();
+  uint64_t bytes() const { return bytes_.load(std::memory_order_relaxed); }
+  uint64_t builds() const { return builds_.load(std::memory_order_relaxed); }
+
+ private:
+  std::mutex mu_;
+  DevBuf buf_;
+  LabelMapTable t_{};
+  uint64_t epoch_ = 0;
+  uint32_t count_ = 0;
+  bool tagged_ = false, usable_ = false;
+  std::atomic<uint64_t> bytes_{0}, builds_{0};
+};
+
 // Results this small are written by the kernels straight into the pinned host buffers (hipHostMalloc memory is
 // mapped into the device's address space): a one-at-a-time query pays no device-to-host copy calls, only the
 // stream synchronisation.  Larger results go through device buffers and one copy each (PCIe bandwidth, not latency).
@@ -182,10 +209,13 @@ class Index {
     out->reset(nq, true);
     return Status::Ok();
   }
-  virtual Status prefilter_stats(vk_prefilter_stats *out) {   // (a sharded index sums its shards)
+  virtual Status prefilter_stats(vk_prefilter_stats_v2 *out) {   // (a sharded index sums its shards)
     pf_.read(out);
+    label_map_counters(&out->label_map_builds, &out->label_map_bytes);
     return Status::Ok();
   }
+  virtual void label_map_counters(uint64_t *builds, uint64_t *bytes) { *builds = 0; *bytes = 0; }   // the index's DeviceLabelMap
+  virtual void release_label_map() {}   // ... given back (a sharded index's resize: its shards' maps)
   // sharded index: its shards (vk_index_shard_device_rows / _commit_device_rows address one of them)
   // the devices a filter of this index must be resident on (FilterSet::build)
   virtual void filter_devices(std::vector<int> *out) const = 0;
@@ -224,8 +254,8 @@ class Index {
   Options opt_;
   // counters of the batched pre-filter search (vk_prefilter_stats)
   struct PrefilterCounters {
-    std::atomic<uint64_t> batches{0}, queries{0}, keys{0}, candidates{0}, fallback_queries{0}, candidate_cap{0};
-    void read(vk_prefilter_stats *out) const {
+    std::atomic<uint64_t> batches{0}, queries{0}, keys{0}, candidates{0}, fallback_queries{0}, candidate_cap{0}, device_resolved_keys{0};
+    void read(vk_prefilter_stats_v2 *out) const {
       const uint64_t sz = out->struct_size;
       memset(out, 0, sizeof(*out));
       out->struct_size = sz;
@@ -235,6 +265,7 @@ class Index {
       out->candidates = candidates.load(std::memory_order_relaxed);
       out->fallback_queries = fallback_queries.load(std::memory_order_relaxed);
       out->candidate_cap = candidate_cap.load(std::memory_order_relaxed);
+      out->device_resolved_keys = device_resolved_keys.load(std::memory_order_relaxed);
     }
   } pf_;
 };
@@ -244,6 +275,13 @@ class Index {
 // synchronise.  The caller holds the index's shared lock and the context's lease.
 Status prefilter_device_stage(SearchCtx *ctx, const void *d_rows, uint32_t dim, uint32_t stride_f, bool l2, bool bf16, const float *queries,
                               uint64_t k, const PrefilterResolved &r, PrefilterCands *out);
+// The same with the label -> slot step on the device (option prefilter-device-resolve): the raw labels are uploaded and
+// label_map.hip's resolve launches write the slots, the segment offsets and the tile offsets that K8b and K8c read; the kept
+// entries' positions come back with the hand-back.  *took = false: the batch has a list beyond the scratch, which the host
+// resolve may still shorten enough -- nothing was done, the caller resolves on the host.  *resolved_keys = keys uploaded.
+Status prefilter_device_stage_keys(SearchCtx *ctx, const LabelMapTable &map, const void *d_rows, uint32_t dim, uint32_t stride_f, bool l2,
+                                   bool bf16, const float *queries, uint64_t nq, uint64_t k, const uint64_t *labels, const uint64_t *list_begin,
+                                   uint64_t n_labels, PrefilterCands *out, bool *took, uint64_t *resolved_keys);
 
 // vk_index_load_tracked: the VectorTracker hook of LoadIndex (bruteforce.h:201, hnswalg.h:1000) -- set by the ABI entry
 // around the load on the loading thread, called by the loaders once per element as it is read from the stream

@@ -456,6 +456,40 @@ struct PrefilterSelectArgs {
 uint32_t prefilter_tiles(uint64_t entries);
 hipError_t launch_prefilter_distance(const PrefilterDistArgs &a, bool l2, bool bf16, hipStream_t s);
 hipError_t launch_prefilter_select(const PrefilterSelectArgs &a, hipStream_t s);
+
+// label_map.hip: the device label map (option prefilter-device-resolve).  An open-addressed table label -> slot, linear
+// probing, the hash and the sizing rule of label_map_hash.hpp; all pointers are device pointers.
+struct LabelMapTable {
+  uint64_t *keys;       // [capacity], UINT64_MAX = empty
+  uint32_t *vals;       // [capacity], written where a key is
+  uint64_t capacity;    // a power of two >= 2 * count
+  unsigned int *fail;   // labels the build could not place (met twice, the empty key, no free bucket)
+};
+// build: every bucket emptied and the failure word cleared on the stream, then slot i < count inserted under labels[i] --
+// unless links0 != nullptr and word links0[i * l0_stride] carries the tombstone bit (HNSW)
+struct LabelMapBuildArgs {
+  LabelMapTable t;
+  const uint64_t *labels;
+  const uint32_t *links0;
+  uint32_t l0_stride, count;
+};
+hipError_t launch_label_map_build(const LabelMapBuildArgs &a, hipStream_t s);
+// resolve: n_seg >= 1 key lists, list s = keys[list_begin[s] .. list_begin[s + 1]) (a shared list is one segment), cut into
+// 256-key tiles: ktile_begin [n_seg + 1] = running label_map_key_tiles() of the lists' lengths, n_ktiles = ktile_begin[n_seg].
+// Out: slot / pos = the known keys' slots and their indices into `keys`, list after list in list order (unknown keys
+// skipped, duplicates kept); seg_begin [n_seg + 1] = the lists' offsets into slot / pos; tile_begin [n_seg + 1] = the running
+// prefilter_tiles() of their lengths -- PrefilterDistArgs' idx, seg_begin and tile_begin.  raw [n_keys] and tile_off
+// [n_ktiles + 1] are scratch.  Three launches on the stream, no host synchronisation.
+struct LabelMapResolveArgs {
+  LabelMapTable t;
+  const uint64_t *keys;
+  const uint32_t *list_begin, *ktile_begin;
+  uint32_t n_seg, n_keys, n_ktiles;
+  uint32_t *raw, *tile_off;
+  uint32_t *seg_begin, *tile_begin, *slot, *pos;
+};
+uint32_t label_map_key_tiles(uint64_t keys);
+hipError_t launch_label_map_resolve(const LabelMapResolveArgs &a, hipStream_t s);
 // the answer of an empty index / shard: out_n = 0, every entry (+inf, kNoLabel)
 // fused re-rank + selection of the candidate filter's survivors (k <= 64): one block per query writes the query's answer
 hipError_t launch_flat_rerank(const FlatScanArgs &a, const MergeArgs &m, bool l2, bool bf16, hipStream_t s);

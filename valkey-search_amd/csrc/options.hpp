@@ -47,6 +47,8 @@ enum OptId : uint32_t {
   kOptHnswNodeMask, kOptHnswNodeMaskBytes,
   // ---- sharded index ---------------------------------------------------------------------------------------------------
   kOptShardThreads, kOptShardAllowStaged,
+  // ---- batched pre-filter search -----------------------------------------------------------------------------------------
+  kOptPrefilterDeviceResolve, kOptPrefilterLabelMapBytes,
   kOptCount
 };
 
@@ -119,6 +121,11 @@ inline const OptDesc &opt_desc(uint32_t id) {
       {"hnsw-node-mask-bytes", nullptr, (uint64_t)1 << 30, 0, kMax},              // ... most device memory a graph's cached masks may hold (least recently used first out)
       {"shard-threads", "VK_SHARD_THREADS", 1, 0, 1},
       {"shard-allow-staged", "VK_SHARD_ALLOW_STAGED", 0, 0, 1},
+      // vk_index_search_labels_batch: label -> slot by the device label map (label_map.hip) instead of one host hash lookup per key;
+      // read per batch, 0 releases the map.  Ships off: it goes on by default only once scripts/prefilter_resolve_probe.py shows no
+      // point below the option-off median
+      {"prefilter-device-resolve", nullptr, 0, 0, 1},
+      {"prefilter-label-map-bytes", nullptr, (uint64_t)1 << 30, 0, kMax},         // ... most device memory an index's (a shard's) label map may hold; a map beyond it is not built: the host resolves
   };
   return t[id];
 }

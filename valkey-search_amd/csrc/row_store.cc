@@ -95,6 +95,7 @@ Status RowStore::bulk_write(uint32_t first, const float *rows, uint64_t n, const
   if (h_labels_.size() < (size_t)first + n) h_labels_.resize((size_t)first + n, ~0ull);
   memcpy(h_labels_.data() + first, labels, n * 8);
   VK_HIP_TRY(hipMemcpyAsync(d_labels_ + first, labels, n * 8, hipMemcpyHostToDevice, stream_));
+  ++label_epoch_;
   VK_HIP_TRY(hipStreamSynchronize(stream_));
   return Status::Ok();
 }
@@ -186,6 +187,7 @@ Status RowStore::flush() {
     if (hi > label_dirty_lo_)
       VK_HIP_TRY(hipMemcpyAsync(d_labels_ + label_dirty_lo_, h_labels_.data() + label_dirty_lo_,
                                 (hi - label_dirty_lo_) * 8, hipMemcpyHostToDevice, stream_));
+    ++label_epoch_;
   }
   VK_HIP_TRY(hipStreamSynchronize(stream_));
   ops_.clear();

@@ -63,6 +63,9 @@ class RowStore {
   void *d_rows_mut() { return d_rows_; }
   const uint64_t *d_labels() const { return d_labels_; }
   uint64_t alloc_rows() const { return alloc_rows_; }
+  // bumped wherever labels reach the device array (flush, bulk_write): what a structure derived from d_labels() -- the
+  // device label map -- is tagged with
+  uint64_t label_epoch() const { return label_epoch_; }
   size_t staged_ops() const { return ops_.size(); }
   size_t staged_bytes() const { return staged_bytes_; }
   bool dirty() const { return !ops_.empty() || label_dirty_lo_ < label_dirty_hi_; }
@@ -108,6 +111,7 @@ class RowStore {
   uint64_t alloc_rows_ = 0;
   std::vector<uint64_t> h_labels_;
   uint64_t label_dirty_lo_ = ~0ull, label_dirty_hi_ = 0;
+  uint64_t label_epoch_ = 1;
   uint64_t written_lo_ = ~0ull, written_hi_ = 0;
   std::vector<Op> ops_;
   std::vector<char *> chunks_;   // pinned staging chunks

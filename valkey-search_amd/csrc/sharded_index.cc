@@ -417,6 +417,7 @@ class ShardedIndex final : public Index {
   Status resize(uint64_t new_max) override {
     std::unique_lock<std::shared_mutex> lk(rw_);
     capacity_ = new_max;
+    for (auto &s : shards_) s->release_label_map();   // (as a plain index's resize does: rebuilt on next use)
     return Status::Ok();
   }
 
@@ -598,16 +599,19 @@ class ShardedIndex final : public Index {
     pf_.candidate_cap.store(prefilter_cap(k), std::memory_order_relaxed);
     return Status::Ok();
   }
-  Status prefilter_stats(vk_prefilter_stats *out) override {   // the shards' sums; the fallbacks are this index's own
+  Status prefilter_stats(vk_prefilter_stats_v2 *out) override {   // the shards' sums; the fallbacks are this index's own
     pf_.read(out);
     for (auto &sh : shards_) {
-      vk_prefilter_stats t;
+      vk_prefilter_stats_v2 t;
       t.struct_size = sizeof(t);
       VK_TRY(sh->prefilter_stats(&t));
       out->batches += t.batches;
       out->queries += t.queries;
       out->keys += t.keys;
       out->candidates += t.candidates;
+      out->device_resolved_keys += t.device_resolved_keys;
+      out->label_map_builds += t.label_map_builds;
+      out->label_map_bytes += t.label_map_bytes;
     }
     return Status::Ok();
   }

@@ -79,6 +79,12 @@ thread_local const vk::LoadObserver *vk::g_load_observer = nullptr;
 namespace {
 thread_local std::string g_last_error;
 
+// what the dispatcher answers a batch of pre-filter requests with (Dispatcher::set_labels_batch)
+vk::Status labels_batch_of(vk::Index *ix, const float *queries, uint64_t nq, uint64_t k, const uint64_t *labels, const uint64_t *list_begin,
+                           uint64_t n_labels, float *out_dist, uint64_t *out_label, uint64_t *out_n) {
+  return ix->search_labels_batch(queries, nq, k, labels, list_begin, n_labels, out_dist, out_label, out_n);
+}
+
 int fail(int code, const std::string &msg) {
   g_last_error = msg;
   return code;
@@ -159,6 +165,7 @@ int vk_index_create(const vk_index_params *params, vk_index **out) {
     *out = new vk_index;
     (*out)->impl = std::move(impl);
     (*out)->dispatcher = std::make_unique<vk::Dispatcher>((*out)->impl.get());
+    (*out)->dispatcher->set_labels_batch(&labels_batch_of);
     sync_dispatcher(*out);
     return vk::Status::Ok();
   });
@@ -343,6 +350,22 @@ int vk_index_search_submit(vk_index *ix, const void *query, uint64_t k, uint64_t
   });
 }
 
+int vk_index_search_labels_submit(vk_index *ix, const void *query, uint64_t k, const uint64_t *labels, uint64_t n_labels, float *out_dist,
+                                  uint64_t *out_label, uint64_t *out_n, vk_search_done_fn done, void *user) {
+  VK_NEED(ix);
+  if (!query || !out_n || !out_dist || !out_label || !done || (n_labels && !labels)) return fail(VK_ERR_INVALID, "NULL argument");
+  if (k == 0) return fail(VK_ERR_INVALID, "k must be positive");
+  if (!ix->dispatcher->enabled())
+    return fail(VK_ERR_INVALID, "vk_index_search_labels_submit needs coalescing (vk_index_set_coalescing with max_batch > 1)");
+  return guarded([&]() -> vk::Status {
+    SubmitCtx *c = new SubmitCtx{ix, done, user, std::chrono::steady_clock::now()};
+    vk::Status st = ix->dispatcher->submit_labels(static_cast<const float *>(query), k, labels, n_labels, out_dist, out_label, out_n,
+                                                  submit_done, c);
+    if (!st.ok()) delete c;   // (not queued: the callback will not fire)
+    return st;
+  });
+}
+
 int vk_index_search_batch_device(vk_index *ix, const void *d_queries, uint64_t nq, uint64_t k, uint64_t ef_runtime,
                                  const uint64_t *d_allow_bits, uint64_t allow_nbits, float *d_out_dist,
                                  uint64_t *d_out_label, uint32_t *d_out_n, void *hip_stream) {
@@ -392,9 +415,18 @@ int vk_index_search_labels_batch(vk_index *ix, const void *queries, uint64_t nq,
 
 int vk_index_prefilter_stats(vk_index *ix, vk_prefilter_stats *out) {
   if (!out) return fail(VK_ERR_INVALID, "out is NULL");
-  if (out->struct_size != sizeof(vk_prefilter_stats)) return fail(VK_ERR_INVALID, "vk_prefilter_stats.struct_size mismatch");
+  const uint64_t size = out->struct_size;   // the struct has grown at its end: an older caller gets the fields it knows
+  if (size != sizeof(vk_prefilter_stats) && size != sizeof(vk_prefilter_stats_v2))
+    return fail(VK_ERR_INVALID, "vk_prefilter_stats.struct_size mismatch");
   VK_NEED(ix);
-  return guarded([&] { return ix->impl->prefilter_stats(out); });
+  return guarded([&] {
+    vk_prefilter_stats_v2 all;
+    all.struct_size = sizeof(all);
+    VK_TRY(ix->impl->prefilter_stats(&all));
+    all.struct_size = size;
+    memcpy(out, &all, (size_t)size);
+    return vk::Status::Ok();
+  });
 }
 
 int vk_index_distance(vk_index *ix, uint64_t label, const void *query, float *out) {
@@ -595,6 +627,7 @@ int vk_index_load_tracked(const vk_index_params *params, vk_read_chunk_fn read_c
     *out = new vk_index;
     (*out)->impl = std::move(impl);
     (*out)->dispatcher = std::make_unique<vk::Dispatcher>((*out)->impl.get());
+    (*out)->dispatcher->set_labels_batch(&labels_batch_of);
     sync_dispatcher(*out);
     return vk::Status::Ok();
   });
