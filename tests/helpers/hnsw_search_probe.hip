@@ -11,6 +11,9 @@
 // Return codes: 0 = done, 1 = the arguments were refused (the kernels trust their caller; nothing refused is launched),
 // 2 = a launch did not finish within kStopSeconds and had to be cancelled through its cancel word (a finding to explain by
 // reading, not a case to re-run), anything else = the source line that saw a HIP error; nothing is retried.
+//
+// hs_probe_rows, at the end, does the same for the two row kernels that close the file (launch_scatter_u32, launch_gather_u32;
+// tests/test_filter_kernels_gpu.py).
 #include "hnsw_search.hip"
 
 #include <string.h>
@@ -337,5 +340,46 @@ extern "C" int hs_probe(const HsGraph *gp, HsLaunch *first, HsLaunch *second) {
   if (int rc = run_one(g, *first, sh, false)) return rc;
   if (second)
     if (int rc = run_one(g, *second, sh, true)) return rc;
+  return 0;
+}
+
+// launch_scatter_u32 (gather = 0: dst[idx[i]][w] = src[i][w], src [n][stride], dst [rows][stride]) or launch_gather_u32
+// (gather = 1: dst[i][w] = src[idx[i]][w], src [rows][stride], dst [n][stride]) for tests/test_filter_kernels_gpu.py: every
+// idx[i] < rows; dst is filled with the pattern first and comes back whole, out_dst [dst words + 2].  These kernels have no
+// cancel word: the stream is polled, and after kStopSeconds the call returns 2 and leaves its buffers where they are.
+extern "C" int hs_probe_rows(uint32_t pattern, int gather, const uint32_t *src, const uint32_t *idx, uint32_t n, uint32_t stride, uint32_t rows,
+                             uint32_t *out_dst) {
+  static bool gave_up = false;
+  if (gave_up || stride == 0 || rows == 0 || (uint64_t)n * stride > (1u << 26) || (uint64_t)rows * stride > (1u << 26)) return 1;
+  for (uint32_t i = 0; i < n; ++i)
+    if (idx[i] >= rows) return 1;
+  const size_t src_words = (size_t)(gather ? rows : n) * stride, dst_words = (size_t)(gather ? n : rows) * stride + 2;
+  DevBuf d_src, d_idx, d_dst;
+  HS_UP(d_src, src, src_words * 4);
+  HS_UP(d_idx, idx, (size_t)n * 4);
+  HS_TRY(d_dst.alloc(dst_words * 4));
+  HS_TRY(d_dst.fill(pattern));
+  HS_TRY(hipDeviceSynchronize());
+  hipStream_t s = nullptr;
+  HS_TRY(hipStreamCreate(&s));
+  int rc = 0;
+  if ((gather ? vk::launch_gather_u32 : vk::launch_scatter_u32)(d_dst.as<uint32_t>(), d_src.as<uint32_t>(), d_idx.as<uint32_t>(), n, stride, s) != hipSuccess)
+    rc = __LINE__;
+  for (const double t0 = now_s(); !rc;) {
+    const hipError_t q = hipStreamQuery(s);
+    if (q == hipSuccess) break;
+    if (q != hipErrorNotReady) rc = __LINE__;
+    else if (now_s() - t0 > kStopSeconds) rc = 2;
+    timespec nap{0, 100000};
+    nanosleep(&nap, nullptr);
+  }
+  if (rc == 2) {   // (a hipFree would wait for the kernel the probe gave up on)
+    gave_up = true;
+    d_src.p = d_idx.p = d_dst.p = nullptr;
+    return rc;
+  }
+  (void)hipStreamDestroy(s);
+  if (rc) return rc;
+  HS_TRY(hipMemcpy(out_dst, d_dst.p, dst_words * 4, hipMemcpyDeviceToHost));
   return 0;
 }
