@@ -114,6 +114,17 @@ class Algo {
       for (uint64_t i = 0; i < n[q]; ++i) out[q].emplace((dist_t)d[q * k + i], (labeltype)l[q * k + i]);
     return out;
   }
+  // ... for a caller that holds device filter handles instead of key arrays (vk_index_search_filter_exact_batch): filters[q] is
+  // query q's handle, each queue is what searchLabels returns over the handle's admitted labels in ascending order
+  std::vector<ResultQueue> searchFilterExactBatch(const void *queries, size_t nq, size_t k, vk_filter *const *filters) const {
+    std::vector<float> d(nq * k + 1);
+    std::vector<uint64_t> l(nq * k + 1), n(nq + 1);
+    Check(vk_index_search_filter_exact_batch(ix_, queries, nq, k, filters, d.data(), l.data(), n.data()));
+    std::vector<ResultQueue> out(nq);
+    for (size_t q = 0; q < nq; ++q)
+      for (uint64_t i = 0; i < n[q]; ++i) out[q].emplace((dist_t)d[q * k + i], (labeltype)l[q * k + i]);
+    return out;
+  }
   // ... submitted (vk_index_search_labels_submit; coalescing on): the request is queued and `done(user, status)` fires once the
   // caller's buffers (k entries each) hold what searchLabels returns; `labels` and the buffers stay valid until then
   void submitLabels(const void *query, size_t k, const uint64_t *labels, size_t n_labels, float *out_dist, uint64_t *out_label, uint64_t *out_n,

@@ -452,6 +452,40 @@ void vk_filter_release(vk_filter *f);
 int vk_filter_info(const vk_filter *f, uint64_t *out_nbits, uint64_t *out_allowed);
 /* the bitmap back on the host: n_words words, zero filled past the filter's end (tests, debugging) */
 int vk_filter_read(const vk_filter *f, uint64_t *out_words, uint64_t n_words);
+/* the admitted labels (the set bits below nbits) back on the host in ascending order, expanded on the device: *out_n = their
+ * number, whatever cap is (size and retry); at most cap entries are written.  Only min(*out_n, cap) labels cross the bus. */
+int vk_filter_read_labels(const vk_filter *f, uint64_t *out_labels, uint64_t cap, uint64_t *out_n);
+/* Exact kNN among the rows a filter handle admits: the pre-filter branch (query::UsePreFiltering, planner.cc:21-45 ->
+ * search.cc:457-481) for a caller that holds a handle and no key array.  filters[q] is query q's handle; consecutive queries
+ * with the same handle form one run, and each run is one device pass: the handle's bitmap is expanded on the device into the
+ * ascending list of its labels, the device label map turns them into row slots, K8b / K8c compute every distance and hand
+ * back each query's entries at or below its k-th smallest, with their labels.  Nothing proportional to the length of the
+ * admitted list crosses the bus in either direction.  Query q's answer is bit for bit what vk_index_search_labels returns
+ * for it over vk_filter_read_labels' list (unknown, removed and tombstoned labels skipped).  Outputs [nq][k] and out_n[nq];
+ * entries past out_n[q] are (+inf, UINT64_MAX).  What the device stage does not cover -- no usable label map (option
+ * prefilter-label-map-bytes), more admitted labels than the scratch holds, k above 4096, more ties at the k-th distance than
+ * the hand-back holds, a NaN distance, a query wider than the distance kernel's LDS (40 960 floats) -- is answered, after one download of the run's list, by
+ * vk_index_search_labels_batch's path: never an error, never another answer.  The label map is used whatever
+ * prefilter-device-resolve says.  A NULL handle, a handle of another index, or nq > 0 with a NULL table is VK_ERR_INVALID
+ * before any device work; nq == 0 does nothing; k == 0 sets every out_n to 0.  Every handle holds a reference for the
+ * duration of the call. */
+int vk_index_search_filter_exact_batch(vk_index *ix, const void *queries, uint64_t nq, uint64_t k, vk_filter *const *filters,
+                                       float *out_dist, uint64_t *out_label, uint64_t *out_n);
+/* Counters of vk_index_search_filter_exact_batch: set struct_size = sizeof(vk_filter_exact_stats) before the call.  On a
+ * sharded index labels_expanded, known_keys and candidates are the sums of the shards' own (every shard expands the copy of
+ * the filter on its device and resolves it against its own label map); the other fields are the index's own. */
+typedef struct vk_filter_exact_stats {
+  uint64_t struct_size;
+  uint64_t batches;            /* calls that reached the index */
+  uint64_t queries;            /* ... and their queries */
+  uint64_t runs;               /* runs of consecutive queries that share a handle */
+  uint64_t labels_expanded;    /* labels written by the expansions (once per run and shard) */
+  uint64_t known_keys;         /* ... of which the label map knew (rows the run's distances were computed over) */
+  uint64_t candidates;         /* entries the device handed back, summed over the queries it answered */
+  uint64_t fallback_queries;   /* queries answered through vk_index_search_labels_batch's path */
+  uint64_t downloaded_runs;    /* runs whose list was downloaded for them */
+} vk_filter_exact_stats;
+int vk_index_filter_exact_stats(vk_index *ix, vk_filter_exact_stats *out);
 /* Cache: filters of one index under a caller-chosen key (e.g. the predicate's canonical text, "@tag:{x}") and EPOCH -- any
  * counter that changes whenever the answer of the predicate may have changed (the module: the count of write phases of the
  * schema's time-sliced mutex, src/index_schema.cc:285-292; finer: a mutation counter of the attribute's own index).  get

@@ -79,6 +79,13 @@ class PrefilterStatsV2(PrefilterStats):
     _fields_ = [("device_resolved_keys", C.c_uint64), ("label_map_builds", C.c_uint64), ("label_map_bytes", C.c_uint64)]
 
 
+class FilterExactStats(C.Structure):
+    """vk_filter_exact_stats"""
+    _fields_ = [("struct_size", C.c_uint64), ("batches", C.c_uint64), ("queries", C.c_uint64), ("runs", C.c_uint64),
+                ("labels_expanded", C.c_uint64), ("known_keys", C.c_uint64), ("candidates", C.c_uint64),
+                ("fallback_queries", C.c_uint64), ("downloaded_runs", C.c_uint64)]
+
+
 class FilterDelta(C.Structure):
     """vk_filter_delta"""
     _fields_ = [("base", C.c_void_p), ("nbits", C.c_uint64), ("clear_labels", C.c_void_p), ("n_clear", C.c_uint64),
@@ -179,6 +186,9 @@ def lib() -> C.CDLL:
     L.vk_filter_release.restype = None
     L.vk_filter_info.argtypes = [vp, u64p, u64p]
     L.vk_filter_read.argtypes = [vp, vp, u64]
+    L.vk_filter_read_labels.argtypes = [vp, vp, u64, u64p]
+    L.vk_index_search_filter_exact_batch.argtypes = [vp, vp, u64, u64, vp, vp, vp, vp]
+    L.vk_index_filter_exact_stats.argtypes = [vp, C.POINTER(FilterExactStats)]
     L.vk_index_filter_cache_get.argtypes = [vp, C.c_char_p, u64, u64, C.POINTER(vp)]
     L.vk_index_filter_cache_put.argtypes = [vp, C.c_char_p, u64, u64, vp]
     L.vk_index_search_filter.argtypes = [vp, vp, u64, u64, vp, vp, i32, vp, vp, u64p]
@@ -258,6 +268,20 @@ class Filter:
         out = np.zeros(max(w, 1), np.uint64)
         _check(lib().vk_filter_read(self._h, _ptr(out), w))
         return out[:w]
+
+    def read_labels(self, cap=None):
+        """vk_filter_read_labels: the admitted labels, ascending (expanded on the device).  cap=None: all of them; else
+        (the first min(total, cap) labels, total)."""
+        n = C.c_uint64()
+        want = self.info()[1] if cap is None else cap
+        out = np.empty(max(want, 1), np.uint64)
+        _check(lib().vk_filter_read_labels(self._h, _ptr(out), want, C.byref(n)))
+        if cap is not None:
+            return out[:min(n.value, cap)], n.value
+        if n.value > want:   # (the device found more than the filter had counted)
+            out = np.empty(n.value, np.uint64)
+            _check(lib().vk_filter_read_labels(self._h, _ptr(out), n.value, C.byref(n)))
+        return out[:n.value]
 
 
 class Index:
@@ -564,6 +588,29 @@ class Index:
         on = np.zeros(max(nq, 1), np.uint64)
         _check(lib().vk_index_search_labels_batch(self._h, _ptr(Q), nq, k, _ptr(labels), _ptr(lb), labels.size, _ptr(od), _ptr(ol), _ptr(on)))
         return od[:, :k], ol[:, :k], on[:nq]
+
+    def search_filter_exact_batch(self, Q, k, filters):
+        """vk_index_search_filter_exact_batch: exact kNN among the rows each query's filter handle admits (one Filter for the
+        whole batch, or one per query; consecutive equal handles form one device pass).  Returns (dist [nq][k], labels [nq][k],
+        n [nq]); row q is what search_labels(Q[q], k, filters[q].read_labels()) returns."""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        nq = Q.shape[0]
+        if isinstance(filters, Filter):
+            filters = [filters] * nq
+        assert len(filters) == nq
+        tab = (C.c_void_p * max(nq, 1))(*[None if f is None else f._h for f in filters])
+        od = np.empty((nq, max(k, 1)), np.float32)
+        ol = np.empty((nq, max(k, 1)), np.uint64)
+        on = np.zeros(max(nq, 1), np.uint64)
+        _check(lib().vk_index_search_filter_exact_batch(self._h, _ptr(Q), nq, k, tab, _ptr(od), _ptr(ol), _ptr(on)))
+        return od[:, :k], ol[:, :k], on[:nq]
+
+    def filter_exact_stats(self) -> FilterExactStats:
+        """the counters of search_filter_exact_batch (vk_index_filter_exact_stats)"""
+        s = FilterExactStats()
+        s.struct_size = C.sizeof(FilterExactStats)
+        _check(lib().vk_index_filter_exact_stats(self._h, C.byref(s)))
+        return s
 
     def prefilter_stats(self) -> PrefilterStats:
         """the counters of search_labels_batch (vk_index_prefilter_stats; a sharded index sums its shards)"""

@@ -31,6 +31,7 @@ class FilterSet {
       if (c.device == device) return c.bits;
     return nullptr;
   }
+  int first_device() const { return copies_.empty() ? -1 : copies_[0].device; }   // where read / filter_read_labels look
   Status read(uint64_t *out_words, uint64_t n_words) const;   // the bitmap back on the host (tests, save)
   // ids: labels in any order, duplicates allowed; runs: [n_runs][2] = first, last (inclusive); host_bits: a bitmap of
   // nbits bits to start from (nullptr = empty).  Labels >= nbits are ignored.  Blocks until every copy is complete.

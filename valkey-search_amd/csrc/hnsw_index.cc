@@ -560,6 +560,26 @@ class HnswIndex final : public Index {
     return Status::Ok();
   }
 
+  // the run of a filter handle: the label map whatever prefilter-device-resolve says (that option governs the list path);
+  // tombstoned nodes are not in the map, so their labels are unknown keys
+  Status handle_candidates(const float *queries, uint64_t nq, uint64_t k, const FilterSet &f, HandleCands *out) override {
+    VK_TRY(flush_if_dirty());
+    std::shared_lock<std::shared_mutex> lk(rw_);
+    (void)hipSetDevice(store_.device());
+    const uint64_t *bits = f.bits_on(store_.device());
+    if (bits == nullptr) return Status::Err(VK_ERR_INVALID, "the filter has no copy on the index's device");
+    CtxLease lease(pool_);
+    LabelMapTable map;
+    const bool have = !store_.dirty() && !graph_->any_dirty() && !links_stale_ && pub_.count <= store_.alloc_rows() &&
+                      label_map_.ready(mask_epoch_, pub_.count, store_.d_labels(), pub_.count ? d_links0_.as<uint32_t>() : nullptr,
+                                       (uint32_t)graph_->maxM0() + 1, opt_.get(kOptPrefilterLabelMapBytes), lease.ctx->stream, &map);
+    uint64_t expanded = 0, known = 0;
+    VK_TRY(prefilter_handle_stage(lease.ctx, have ? &map : nullptr, bits, f.nbits(), f.allowed(), store_.d_rows(), params_.dim, store_.stride_f(),
+                                  l2(), store_.bf16(), queries, nq, k, out, &expanded, &known));
+    count_handle_stage(*out, expanded, known);
+    return Status::Ok();
+  }
+
   Status distance(uint64_t label, const float *query, float *out) override {
     float d;
     uint64_t l, n = 0;

@@ -20,6 +20,7 @@
 #include "filter_set.hpp"
 #include "kernels.hpp"
 #include "options.hpp"
+#include "prefilter_handle_host.hpp"
 #include "prefilter_host.hpp"
 #include "row_store.hpp"
 
@@ -215,6 +216,21 @@ class Index {
     return Status::Ok();
   }
   virtual void label_map_counters(uint64_t *builds, uint64_t *bytes) { *builds = 0; *bytes = 0; }   // the index's DeviceLabelMap
+  // vk_index_search_filter_exact_batch: exact kNN among the rows filter handles admit, each answer bit for bit search_labels'
+  // over the handle's ascending label list (prefilter_handle.cc).  tab[q] is query q's filter; consecutive queries with the
+  // same one form a run, and a run is one handle_candidates -- the shard-level call: per query every entry at or below its
+  // k-th smallest distance with its label, in label order, or the mark "take the list path".  An index without a device
+  // stage marks every query.
+  Status search_filter_exact_batch(const float *queries, uint64_t nq, uint64_t k, const FilterSet *const *tab, float *out_dist,
+                                   uint64_t *out_label, uint64_t *out_n);
+  virtual Status handle_candidates(const float *, uint64_t nq, uint64_t, const FilterSet &, HandleCands *out) {
+    out->reset(nq, true);
+    return Status::Ok();
+  }
+  virtual Status filter_exact_stats(vk_filter_exact_stats *out) {   // (a sharded index adds its shards' device counters)
+    hx_.read(out);
+    return Status::Ok();
+  }
   virtual void release_label_map() {}   // ... given back (a sharded index's resize: its shards' maps)
   // sharded index: its shards (vk_index_shard_device_rows / _commit_device_rows address one of them)
   // the devices a filter of this index must be resident on (FilterSet::build)
@@ -268,6 +284,32 @@ class Index {
       out->device_resolved_keys = device_resolved_keys.load(std::memory_order_relaxed);
     }
   } pf_;
+  // ... and of the exact search from filter handles (vk_filter_exact_stats)
+  struct HandleCounters {
+    std::atomic<uint64_t> batches{0}, queries{0}, runs{0}, labels_expanded{0}, known_keys{0}, candidates{0}, fallback_queries{0},
+        downloaded_runs{0};
+    void read(vk_filter_exact_stats *out) const {
+      memset(out, 0, sizeof(*out));
+      out->struct_size = sizeof(*out);
+      out->batches = batches.load(std::memory_order_relaxed);
+      out->queries = queries.load(std::memory_order_relaxed);
+      out->runs = runs.load(std::memory_order_relaxed);
+      out->labels_expanded = labels_expanded.load(std::memory_order_relaxed);
+      out->known_keys = known_keys.load(std::memory_order_relaxed);
+      out->candidates = candidates.load(std::memory_order_relaxed);
+      out->fallback_queries = fallback_queries.load(std::memory_order_relaxed);
+      out->downloaded_runs = downloaded_runs.load(std::memory_order_relaxed);
+    }
+  } hx_;
+  // what a leaf's handle_candidates adds after its device stage
+  void count_handle_stage(const HandleCands &c, uint64_t expanded, uint64_t known) {
+    uint64_t cands = 0;
+    for (size_t q = 0; q < c.fallback.size(); ++q)
+      if (!c.fallback[q]) cands += c.begin[q + 1] - c.begin[q];
+    hx_.labels_expanded.fetch_add(expanded, std::memory_order_relaxed);
+    hx_.known_keys.fetch_add(known, std::memory_order_relaxed);
+    hx_.candidates.fetch_add(cands, std::memory_order_relaxed);
+  }
 };
 
 // The device stage of prefilter_candidates on one device, for lists already resolved to row slots (prefilter_batch.cc):
@@ -282,6 +324,19 @@ Status prefilter_device_stage(SearchCtx *ctx, const void *d_rows, uint32_t dim, 
 Status prefilter_device_stage_keys(SearchCtx *ctx, const LabelMapTable &map, const void *d_rows, uint32_t dim, uint32_t stride_f, bool l2,
                                    bool bf16, const float *queries, uint64_t nq, uint64_t k, const uint64_t *labels, const uint64_t *list_begin,
                                    uint64_t n_labels, PrefilterCands *out, bool *took, uint64_t *resolved_keys);
+
+// The device stage of handle_candidates on one device (prefilter_handle.cc): the filter's bitmap expanded into the ascending
+// list of its labels in the context's scratch (filter_expand.hip), that list resolved by label_map.hip's three launches as one
+// shared segment, K8b and K8c as prefilter_device_stage_keys launches them, one gather of the candidates' labels, and a
+// download of counts, candidates and candidate labels only.  map == nullptr (no usable label map), an admitted count beyond
+// the scratch or different from the device's total, k beyond the hand-back, a query wider than K8b's LDS: every query is
+// marked.  *expanded = labels the expansion wrote, *known = entries of the resolved list.  The caller holds the index's
+// shared lock and the context's lease.
+Status prefilter_handle_stage(SearchCtx *ctx, const LabelMapTable *map, const uint64_t *d_bits, uint64_t nbits, uint64_t allowed,
+                              const void *d_rows, uint32_t dim, uint32_t stride_f, bool l2, bool bf16, const float *queries, uint64_t nq,
+                              uint64_t k, HandleCands *out, uint64_t *expanded, uint64_t *known);
+// vk_filter_read_labels, and the fallback's download: the filter's first copy expanded on its device's build lane
+Status filter_read_labels(const FilterSet &f, uint64_t *out_labels, uint64_t cap, uint64_t *out_n);
 
 // vk_index_load_tracked: the VectorTracker hook of LoadIndex (bruteforce.h:201, hnswalg.h:1000) -- set by the ABI entry
 // around the load on the loading thread, called by the loaders once per element as it is read from the stream

@@ -523,6 +523,19 @@ hipError_t launch_filter_delta_copy(const uint64_t *d_items, uint32_t n, uint64_
 hipError_t launch_filter_delta_apply(const uint64_t *d_items, const uint64_t *d_recs, uint64_t n_recs, int set, unsigned long long *d_counts,
                                      hipStream_t s);
 
+// filter_expand.hip: labels[0 .. min(total, cap)) = the set bits of `bits` below nbits as u64 labels, ascending; *total = their
+// number.  Bits at or above nbits in the last word are ignored and no word past (nbits + 63) / 64 is read; nothing is written
+// at or past cap.  tile_off [filter_expand_tiles(nbits)] is scratch.  Three launches on the stream, no host synchronisation.
+uint32_t filter_expand_tiles(uint64_t nbits);
+uint32_t filter_expand_tile_words();   // bitmap words per block of the count / emit launches
+uint32_t filter_expand_scan_trip();    // tiles the one-block scan takes per trip
+hipError_t launch_filter_expand(const uint64_t *bits, uint64_t nbits, uint64_t cap, uint64_t *labels, unsigned long long *total,
+                                unsigned long long *tile_off, hipStream_t s);
+// ... and behind K8c: out[q][i] = keys[pos[cand[q][i].x]] for i < count[q], for every query whose count word is at most cap
+// (cand, count as PrefilterSelectArgs; pos as LabelMapResolveArgs; list_len = entries of the resolved list; nq <= 65535)
+hipError_t launch_filter_gather_labels(const uint32_t *count, const uint2 *cand, const uint32_t *pos, const uint64_t *keys, uint32_t list_len,
+                                       uint32_t nq, uint32_t cap, uint64_t *out, hipStream_t s);
+
 // node_mask.hip: n device filters translated into the graph's internal-id space in one launch.  d_items [n][kNodeMaskItemWords]
 // = {filter bits, nbits, dst} (device pointers); dst[i / 64] bit i % 64 = live bit i && label[i] < nbits && filter bit label[i],
 // every one of the (count + 63) / 64 words of dst is written (bits past count are 0); d_counts [n] (zeroed by the caller) += the

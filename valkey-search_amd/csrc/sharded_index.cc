@@ -616,6 +616,31 @@ class ShardedIndex final : public Index {
     return Status::Ok();
   }
 
+  // The run of a filter handle: every shard expands the copy of the filter on its device and resolves the list against its own
+  // label map -- the labels of other shards are simply unknown there -- and runs the stage with the same k (the superset
+  // argument of prefilter_candidates); the union back in label order.  A query any shard hands over is handed over.
+  Status handle_candidates(const float *queries, uint64_t nq, uint64_t k, const FilterSet &f, HandleCands *out) override {
+    std::vector<HandleCands> parts(shards_.size());
+    for (size_t s = 0; s < shards_.size(); ++s) {
+      VK_TRY(shards_[s]->handle_candidates(queries, nq, k, f, &parts[s]));
+      if (parts[s].fallback.size() != nq || parts[s].begin.size() != nq + 1)
+        return Status::Err(VK_ERR_INTERNAL, "prefilter: malformed shard handle candidates");
+    }
+    handle_union(parts, nq, out);
+    return Status::Ok();
+  }
+  Status filter_exact_stats(vk_filter_exact_stats *out) override {   // the shards' device counters summed; the rest is this index's own
+    hx_.read(out);
+    for (auto &sh : shards_) {
+      vk_filter_exact_stats t;
+      VK_TRY(sh->filter_exact_stats(&t));
+      out->labels_expanded += t.labels_expanded;
+      out->known_keys += t.known_keys;
+      out->candidates += t.candidates;
+    }
+    return Status::Ok();
+  }
+
   Status distance(uint64_t label, const float *query, float *out) override {
     uint32_t s;
     if (!route_of(label, &s)) return Status::Err(VK_ERR_NOT_FOUND, "Couldn't find internal id");

@@ -752,6 +752,41 @@ int vk_filter_read(const vk_filter *f, uint64_t *out_words, uint64_t n_words) {
   return guarded([&] { return f->set->read(out_words, n_words); });
 }
 
+int vk_filter_read_labels(const vk_filter *f, uint64_t *out_labels, uint64_t cap, uint64_t *out_n) {
+  if (!f || !out_n || (cap && !out_labels)) return fail(VK_ERR_INVALID, "NULL argument");
+  return guarded([&] { return vk::filter_read_labels(*f->set, out_labels, cap, out_n); });
+}
+
+int vk_index_search_filter_exact_batch(vk_index *ix, const void *queries, uint64_t nq, uint64_t k, vk_filter *const *filters, float *out_dist,
+                                       uint64_t *out_label, uint64_t *out_n) {
+  // every argument error before the index is touched
+  VK_NEED(ix);
+  if (nq == 0) return VK_OK;
+  if (!queries || !filters || !out_n) return fail(VK_ERR_INVALID, "queries/filters/out_n is NULL");
+  if (k && (!out_dist || !out_label)) return fail(VK_ERR_INVALID, "output buffers are NULL");
+  for (uint64_t q = 0; q < nq; ++q) {
+    if (!filters[q]) return fail(VK_ERR_INVALID, "a filter handle is NULL");
+    if (filters[q]->owner != ix) return fail(VK_ERR_INVALID, "the filter belongs to another index");
+  }
+  return guarded([&] {
+    // a reference on every handle in use for the duration of the call (the caller may drop its own at any time)
+    std::vector<std::shared_ptr<vk::FilterSet>> held;
+    std::vector<const vk::FilterSet *> tab(nq);
+    for (uint64_t q = 0; q < nq; ++q) {
+      if (q == 0 || filters[q] != filters[q - 1]) held.push_back(filters[q]->set);
+      tab[q] = held.back().get();
+    }
+    return ix->impl->search_filter_exact_batch(static_cast<const float *>(queries), nq, k, tab.data(), out_dist, out_label, out_n);
+  });
+}
+
+int vk_index_filter_exact_stats(vk_index *ix, vk_filter_exact_stats *out) {
+  if (!out) return fail(VK_ERR_INVALID, "out is NULL");
+  if (out->struct_size != sizeof(vk_filter_exact_stats)) return fail(VK_ERR_INVALID, "vk_filter_exact_stats.struct_size mismatch");
+  VK_NEED(ix);
+  return guarded([&] { return ix->impl->filter_exact_stats(out); });
+}
+
 int vk_index_filter_cache_get(vk_index *ix, const void *key, uint64_t key_len, uint64_t epoch, vk_filter **out) {
   VK_NEED(ix);
   if (!out || (key_len && !key)) return fail(VK_ERR_INVALID, "NULL argument");
