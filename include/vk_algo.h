@@ -151,7 +151,14 @@ class Algo {
     Check(vk_index_get_stats(ix_, &s));
     return s;
   }
-  void flush() { Check(vk_index_flush(ix_)); }                                // write -> read phase switch
+  // the counters of the FLAT searches with k > 1024 (vk_index_large_k_stats; option flat-large-k = 1: one row pass per chunk)
+  vk_flat_large_k_stats largeKStats() const {
+    vk_flat_large_k_stats s;
+    s.struct_size = sizeof(s);
+    Check(vk_index_large_k_stats(ix_, &s));
+    return s;
+  }
+  void flush() { Check(vk_index_flush(ix_)); }                             // write -> read phase switch
   void setCoalescing(uint32_t max_batch, uint32_t max_wait_us) { Check(vk_index_set_coalescing(ix_, max_batch, max_wait_us)); }
   vk_index *handle() const { return ix_; }
   const vk_index_params &params() const { return params_; }

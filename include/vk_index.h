@@ -486,6 +486,22 @@ typedef struct vk_filter_exact_stats {
   uint64_t downloaded_runs;    /* runs whose list was downloaded for them */
 } vk_filter_exact_stats;
 int vk_index_filter_exact_stats(vk_index *ix, vk_filter_exact_stats *out);
+/* Counters of the FLAT searches with k > 1024 (after the clamp to the index's count), totals since creation: set struct_size =
+ * sizeof(vk_flat_large_k_stats) before the call.  With option flat-large-k = 1 such a search is one dense distance pass per
+ * chunk of queries, a device select of each query's k-th key and a host finish; with 0 (the default), for a table whose one
+ * row of distances is beyond flat-large-k-bytes, and for a query with more ties at its k-th distance than the hand-back holds,
+ * it is the paged path: one scan of the table per 1024 results.  Both give the same bytes.  An HNSW index answers zeros, a
+ * sharded index the sums of its shards (every shard serves its own large-k search). */
+typedef struct vk_flat_large_k_stats {
+  uint64_t struct_size;
+  uint64_t queries;            /* queries with k > 1024, whatever served them */
+  uint64_t one_pass_queries;   /* ... answered by the one-pass path */
+  uint64_t fallback_queries;   /* ... sent to the paged path by the one-pass path (ties beyond the hand-back, the byte budget) */
+  uint64_t chunks;             /* chunks of queries the one-pass path ran */
+  uint64_t emitted_entries;    /* entries handed back by the device, summed over one_pass_queries */
+  uint64_t row_passes;         /* scans of the whole table: one per chunk, one per pass of the paged path */
+} vk_flat_large_k_stats;
+int vk_index_large_k_stats(vk_index *ix, vk_flat_large_k_stats *out);
 /* Cache: filters of one index under a caller-chosen key (e.g. the predicate's canonical text, "@tag:{x}") and EPOCH -- any
  * counter that changes whenever the answer of the predicate may have changed (the module: the count of write phases of the
  * schema's time-sliced mutex, src/index_schema.cc:285-292; finer: a mutation counter of the attribute's own index).  get

@@ -86,6 +86,12 @@ class FilterExactStats(C.Structure):
                 ("fallback_queries", C.c_uint64), ("downloaded_runs", C.c_uint64)]
 
 
+class FlatLargeKStats(C.Structure):
+    """vk_flat_large_k_stats"""
+    _fields_ = [("struct_size", C.c_uint64), ("queries", C.c_uint64), ("one_pass_queries", C.c_uint64), ("fallback_queries", C.c_uint64),
+                ("chunks", C.c_uint64), ("emitted_entries", C.c_uint64), ("row_passes", C.c_uint64)]
+
+
 class FilterDelta(C.Structure):
     """vk_filter_delta"""
     _fields_ = [("base", C.c_void_p), ("nbits", C.c_uint64), ("clear_labels", C.c_void_p), ("n_clear", C.c_uint64),
@@ -189,6 +195,7 @@ def lib() -> C.CDLL:
     L.vk_filter_read_labels.argtypes = [vp, vp, u64, u64p]
     L.vk_index_search_filter_exact_batch.argtypes = [vp, vp, u64, u64, vp, vp, vp, vp]
     L.vk_index_filter_exact_stats.argtypes = [vp, C.POINTER(FilterExactStats)]
+    L.vk_index_large_k_stats.argtypes = [vp, C.POINTER(FlatLargeKStats)]
     L.vk_index_filter_cache_get.argtypes = [vp, C.c_char_p, u64, u64, C.POINTER(vp)]
     L.vk_index_filter_cache_put.argtypes = [vp, C.c_char_p, u64, u64, vp]
     L.vk_index_search_filter.argtypes = [vp, vp, u64, u64, vp, vp, i32, vp, vp, u64p]
@@ -610,6 +617,13 @@ class Index:
         s = FilterExactStats()
         s.struct_size = C.sizeof(FilterExactStats)
         _check(lib().vk_index_filter_exact_stats(self._h, C.byref(s)))
+        return s
+
+    def large_k_stats(self) -> FlatLargeKStats:
+        """the counters of the FLAT searches with k > 1024 (vk_index_large_k_stats; option flat-large-k)"""
+        s = FlatLargeKStats()
+        s.struct_size = C.sizeof(FlatLargeKStats)
+        _check(lib().vk_index_large_k_stats(self._h, C.byref(s)))
         return s
 
     def prefilter_stats(self) -> PrefilterStats:

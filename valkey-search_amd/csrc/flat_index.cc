@@ -23,6 +23,7 @@
 #include <queue>
 #include <thread>
 
+#include "flat_large_k_host.hpp"
 #include "index.hpp"
 
 namespace vk {
@@ -96,9 +97,9 @@ SearchCtx::~SearchCtx() {
   if (busy) (void)hipEventDestroy(busy);
   if (stream) (void)hipStreamSynchronize(stream);
   for (DevBuf *b : {&d_q, &d_part_d, &d_part_l, &d_out_d, &d_out_l, &d_out_n, &d_allow, &d_idx, &d_tmp, &d_stats, &d_sync, &d_pool, &d_pool2, &d_redo,
-                    &d_fq16, &d_fthr, &d_fcnt, &d_fcand, &d_fspill, &d_fsmax, &d_fpart_d, &d_fpart_l, &d_allow_tab})
+                    &d_fq16, &d_fthr, &d_fcnt, &d_fcand, &d_fspill, &d_fsmax, &d_fpart_d, &d_fpart_l, &d_allow_tab, &d_lk_dist, &d_lk_work})
     b->release();
-  for (PinBuf *b : {&h_q, &h_out_d, &h_out_l, &h_out_n, &h_tmp, &h_idx, &h_cancel}) b->release();
+  for (PinBuf *b : {&h_q, &h_out_d, &h_out_l, &h_out_n, &h_tmp, &h_idx, &h_cancel, &h_lk}) b->release();
   if (stream) (void)hipStreamDestroy(stream);
 }
 
@@ -381,7 +382,11 @@ class FlatIndex final : public Index {
     VK_TRY(upload_queries(ctx, rq.queries, rq.nq, params_.dim, store_.stride_f(), opt_.get(kOptUploadParallel) != 0, rq.query_tab));
     const uint64_t *d_allow = d_filter;
     if (!d_filter) VK_TRY(upload_allow(ctx, rq.allow_bits, rq.allow_nbits, &d_allow));
-    if (k > kMaxPassK) return search_in_passes(ctx, rq, k, count, d_allow, out_dist, out_label, out_n);
+    if (k > kMaxPassK) {
+      lk_.queries.fetch_add(rq.nq, std::memory_order_relaxed);
+      if (opt_.get(kOptFlatLargeK) != 0) return search_large_k(ctx, rq, k, count, d_allow, out_dist, out_label, out_n);
+      return search_in_passes(ctx, rq, k, count, d_allow, out_dist, out_label, out_n);
+    }
     VK_TRY(ctx->h_out_d.ensure(rq.nq * k * 4));
     VK_TRY(ctx->h_out_l.ensure(rq.nq * k * 8));
     VK_TRY(ctx->h_out_n.ensure(rq.nq * 4));
@@ -807,6 +812,7 @@ class FlatIndex final : public Index {
       lb_dist_ = nullptr;
       lb_label_ = nullptr;
       VK_TRY(st);
+      lk_.row_passes.fetch_add(1, std::memory_order_relaxed);   // (vk_flat_large_k_stats: a counter, nothing reads it here)
       VK_HIP_TRY(hipMemcpyAsync(ctx->h_out_d.p, ctx->d_out_d.p, nq * kp * 4, hipMemcpyDeviceToHost, ctx->stream));
       VK_HIP_TRY(hipMemcpyAsync(ctx->h_out_l.p, ctx->d_out_l.p, nq * kp * 8, hipMemcpyDeviceToHost, ctx->stream));
       VK_HIP_TRY(hipMemcpyAsync(ctx->h_out_n.p, ctx->d_out_n.p, nq * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -824,6 +830,113 @@ class FlatIndex final : public Index {
       first = false;
     }
     for (uint64_t q = 0; q < nq; ++q) out_n[q] = got[q];
+    return Status::Ok();
+  }
+
+  // k > 1024 with option flat-large-k (flat_large_k.hip, flat_large_k_host.hpp): per chunk of queries ONE dense distance pass
+  // over the rows, the radix select of every query's k-th key, the emit of what lies at or below it, one download (state words,
+  // labels, distance bits) into the context's pinned block and one synchronise; the host orders each hand-back by (distance,
+  // label) and cuts it at k -- the bytes search_in_passes returns.  A query flagged by the device (more ties at its k-th key
+  // than the hand-back holds) is answered by search_in_passes afterwards, restricted to those queries; a table whose one row of
+  // distances is beyond flat-large-k-bytes (or whose k is beyond 32-bit slots) goes there whole.  Cancellation: as the paged
+  // path, none.
+  Status search_large_k(SearchCtx *ctx, const SearchRequest &rq, uint64_t k, uint64_t count, const uint64_t *d_allow, float *out_dist,
+                        uint64_t *out_label, uint64_t *out_n) {
+    const uint64_t nq = rq.nq;
+    const uint32_t chunks = store_.stride_f() / 16;
+    const LargeKPlan plan = large_k_plan(nq, count, k, opt_.get(kOptFlatLargeKBytes));
+    const uint64_t cap = large_k_cap(k);
+    if (!plan.fits || cap > 0xFFFFFFFFull || count > 0xFFFFFFFFull || (size_t)chunks * 64 > 160 * 1024) {
+      lk_.fallback_queries.fetch_add(nq, std::memory_order_relaxed);
+      return search_in_passes(ctx, rq, k, count, d_allow, out_dist, out_label, out_n);
+    }
+    const size_t per_q_back = (size_t)kLargeKStateWords * 4 + (size_t)cap * kLargeKSlotBytes;   // downloaded
+    VK_TRY(ctx->d_lk_dist.ensure((size_t)plan.chunk_q * plan.ld * 4));
+    VK_TRY(ctx->d_lk_work.ensure((size_t)plan.chunk_q * (per_q_back + (size_t)kLargeKBins * 4)));
+    VK_TRY(ctx->h_lk.ensure((size_t)plan.chunk_q * per_q_back));
+    std::vector<uint64_t> redo;
+    for (uint64_t q0 = 0; q0 < nq; q0 += plan.chunk_q) {
+      const uint64_t qc = std::min<uint64_t>(plan.chunk_q, nq - q0);
+      // the chunk's block: [qc] state | [qc][cap] labels | [qc][cap] distance bits -- downloaded as one piece -- | [qc] histograms
+      char *w = ctx->d_lk_work.as<char>();
+      FlatLargeKArgs a{};
+      a.rows = store_.d_rows();
+      a.labels = store_.d_labels();
+      a.queries = ctx->d_q.as<float>() + (size_t)q0 * store_.stride_f();
+      a.allow_bits = d_allow;
+      a.allow_nbits = rq.allow_nbits;
+      a.row_stride_f = a.q_stride_f = store_.stride_f();
+      a.chunks = chunks;
+      a.count = (uint32_t)count;
+      a.qc = (uint32_t)qc;
+      a.k = (uint32_t)k;
+      a.cap = (uint32_t)cap;
+      a.ld = plan.ld;
+      a.dist = ctx->d_lk_dist.as<float>();
+      a.state = reinterpret_cast<uint32_t *>(w);
+      a.out_label = reinterpret_cast<uint64_t *>(w + qc * kLargeKStateWords * 4);
+      a.out_bits = reinterpret_cast<uint32_t *>(w + qc * kLargeKStateWords * 4 + qc * cap * 8);
+      a.hist = reinterpret_cast<uint32_t *>(w + qc * per_q_back);
+      VK_HIP_TRY(hipMemsetAsync(a.hist, 0, qc * kLargeKBins * 4, ctx->stream));
+      VK_HIP_TRY(launch_flat_large_k_distance(a, l2(), store_.bf16(), flat_scan_pick_qb(qc, chunks, 1, l2()), ctx->stream));
+      VK_HIP_TRY(launch_flat_large_k_select(a, ctx->stream));
+      VK_HIP_TRY(launch_flat_large_k_emit(a, ctx->stream));
+      VK_HIP_TRY(hipMemcpyAsync(ctx->h_lk.p, w, qc * per_q_back, hipMemcpyDeviceToHost, ctx->stream));
+      VK_HIP_TRY(hipStreamSynchronize(ctx->stream));
+      lk_.chunks.fetch_add(1, std::memory_order_relaxed);
+      lk_.row_passes.fetch_add(1, std::memory_order_relaxed);
+      const char *h = ctx->h_lk.as<char>();
+      const uint32_t *h_state = reinterpret_cast<const uint32_t *>(h);
+      const uint64_t *h_label = reinterpret_cast<const uint64_t *>(h + qc * kLargeKStateWords * 4);
+      const uint32_t *h_bits = reinterpret_cast<const uint32_t *>(h + qc * kLargeKStateWords * 4 + qc * cap * 8);
+      uint64_t emitted = 0, served = 0;
+      for (uint64_t q = 0; q < qc; ++q) {
+        const uint32_t *st = h_state + q * kLargeKStateWords;   // T | k left | n_less | n_eq | n_real | counter | flag | 0
+        if (st[6]) {
+          redo.push_back(q0 + q);
+          continue;
+        }
+        const uint64_t n = (uint64_t)st[2] + st[3];
+        if (n > cap || st[5] != n) return Status::Err(VK_ERR_INTERNAL, "flat-large-k: the emit count does not match the select");
+        out_n[q0 + q] = large_k_finish(h_bits + q * cap, h_label + q * cap, n, k, out_dist + (q0 + q) * rq.k, out_label + (q0 + q) * rq.k);
+        emitted += n;
+        ++served;
+      }
+      lk_.emitted_entries.fetch_add(emitted, std::memory_order_relaxed);
+      lk_.one_pass_queries.fetch_add(served, std::memory_order_relaxed);
+    }
+    if (redo.empty()) return Status::Ok();
+    // the flagged queries through the paged path: their vectors take the front of the query block, their answers come back
+    // through lists of their own
+    lk_.fallback_queries.fetch_add(redo.size(), std::memory_order_relaxed);
+    const uint64_t nr = redo.size();
+    std::vector<const float *> tab(nr);
+    for (uint64_t i = 0; i < nr; ++i) tab[i] = rq.query_tab ? rq.query_tab[redo[i]] : rq.queries + redo[i] * params_.dim;
+    VK_TRY(upload_queries(ctx, nullptr, nr, params_.dim, store_.stride_f(), false, tab.data()));
+    SearchRequest sub = rq;
+    sub.nq = nr;
+    sub.queries = nullptr;
+    sub.query_tab = tab.data();
+    std::vector<float> td(nr * rq.k);
+    std::vector<uint64_t> tl(nr * rq.k), tn(nr);
+    VK_TRY(search_in_passes(ctx, sub, k, count, d_allow, td.data(), tl.data(), tn.data()));
+    for (uint64_t i = 0; i < nr; ++i) {
+      out_n[redo[i]] = tn[i];
+      memcpy(out_dist + redo[i] * rq.k, td.data() + i * rq.k, (size_t)tn[i] * 4);
+      memcpy(out_label + redo[i] * rq.k, tl.data() + i * rq.k, (size_t)tn[i] * 8);
+    }
+    return Status::Ok();
+  }
+
+  Status large_k_stats(vk_flat_large_k_stats *out) override {
+    memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    out->queries = lk_.queries.load(std::memory_order_relaxed);
+    out->one_pass_queries = lk_.one_pass_queries.load(std::memory_order_relaxed);
+    out->fallback_queries = lk_.fallback_queries.load(std::memory_order_relaxed);
+    out->chunks = lk_.chunks.load(std::memory_order_relaxed);
+    out->emitted_entries = lk_.emitted_entries.load(std::memory_order_relaxed);
+    out->row_passes = lk_.row_passes.load(std::memory_order_relaxed);
     return Status::Ok();
   }
 
@@ -1365,6 +1478,10 @@ class FlatIndex final : public Index {
   static thread_local bool filter_used_;
   static constexpr uint64_t kGemmMinQueries = 5;    // measured at 10Mx768: K3 4 queries 5.3 ms, 8 queries 11.7 ms; K4 up to 32 queries 6.1 ms
   static constexpr uint64_t kMaxPassK = 1024;
+  // counters of the searches with k > kMaxPassK (vk_flat_large_k_stats)
+  struct LargeKCounters {
+    std::atomic<uint64_t> queries{0}, one_pass_queries{0}, fallback_queries{0}, chunks{0}, emitted_entries{0}, row_passes{0};
+  } lk_;
   // per-call lower bounds of search_in_passes (set only around its scan() calls, under the ctx lease)
   static thread_local const float *lb_dist_;
   static thread_local const uint64_t *lb_label_;

@@ -81,11 +81,12 @@ struct SearchCtx {
   DevBuf d_q, d_part_d, d_part_l, d_out_d, d_out_l, d_out_n, d_allow, d_idx, d_tmp, d_stats, d_sync, d_pool, d_pool2, d_redo,
       d_fq16, d_fthr, d_fcnt, d_fcand, d_fspill, d_fsmax, d_fpart_d, d_fpart_l,   // candidate filter (flat_filter.hip)
       d_allow_tab,                                             // per-query filter table + the bitmaps behind it
-      d_mask;                                                  // HNSW node masks: build items + counts, per-query mask table
+      d_mask,                                                  // HNSW node masks: build items + counts, per-query mask table
+      d_lk_dist, d_lk_work;                                    // FLAT k > 1024 in one pass: distances | state, hand-back lists, histograms
   // what the work enqueued last must outlive although its caller may let go of it (node masks of a device-buffer search);
   // replaced by the context's next user
   std::vector<std::shared_ptr<const void>> keep_alive;
-  PinBuf h_q, h_out_d, h_out_l, h_out_n, h_tmp, h_idx, h_cancel;
+  PinBuf h_q, h_out_d, h_out_l, h_out_n, h_tmp, h_idx, h_cancel, h_lk;
   // per-member cancellation (SearchRequest::member_cancel): the words the kernel polls follow the batch word in h_cancel
   static constexpr size_t kMemberCancelOffset = 16;   // in u32 words
   Status wait(const volatile int *caller_flag, const volatile uint32_t *member_cancel, uint64_t nq);
@@ -229,6 +230,12 @@ class Index {
   }
   virtual Status filter_exact_stats(vk_filter_exact_stats *out) {   // (a sharded index adds its shards' device counters)
     hx_.read(out);
+    return Status::Ok();
+  }
+  // vk_index_large_k_stats (FLAT; a sharded index sums its shards, HNSW answers zeros)
+  virtual Status large_k_stats(vk_flat_large_k_stats *out) {
+    memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
     return Status::Ok();
   }
   virtual void release_label_map() {}   // ... given back (a sharded index's resize: its shards' maps)

@@ -536,6 +536,35 @@ hipError_t launch_filter_expand(const uint64_t *bits, uint64_t nbits, uint64_t c
 hipError_t launch_filter_gather_labels(const uint32_t *count, const uint2 *cand, const uint32_t *pos, const uint64_t *keys, uint32_t list_len,
                                        uint32_t nq, uint32_t cap, uint64_t *out, hipStream_t s);
 
+// flat_large_k.hip: FLAT k > 1024 in one row pass (option flat-large-k).  For a chunk of qc queries: a dense distance pass
+// (dist[q][row], NaN = not a candidate), a radix select of every query's k-th key over merge_key's u32 (three digits, a
+// histogram launch and a pick launch each), and an emit of every candidate at or below that key.  All pointers are device
+// pointers; every stage is its own launch, ordered by the stream.
+constexpr uint32_t kLargeKBins = 2048;        // histogram words per query (the widest digit)
+constexpr uint32_t kLargeKStateWords = 8;     // per query: T | k left | n_less | n_eq | n_real | emit counter | overflow flag | 0
+struct FlatLargeKArgs {
+  const void *rows;           // f32 or bf16 rows, row_stride_f elements apart
+  const uint64_t *labels;     // [count]
+  const float *queries;       // [qc][q_stride_f] padded
+  const uint64_t *allow_bits; // optional bitmap by label
+  uint64_t allow_nbits;
+  uint32_t row_stride_f, q_stride_f, chunks;
+  uint32_t count;             // rows [0, count), >= 1
+  uint32_t qc;                // queries of the chunk, <= 65535
+  uint32_t k, cap;            // cap = large_k_cap(k): slots per query of the hand-back
+  uint64_t ld;                // floats between two queries' rows of dist, >= count
+  float *dist;                // [qc][ld]; nothing is written at or beyond count
+  uint32_t *hist;             // [qc][kLargeKBins], zeroed before launch_flat_large_k_select (which leaves it zeroed)
+  uint32_t *state;            // [qc][kLargeKStateWords], written whole by the select
+  uint32_t *out_bits;         // [qc][cap] distance bits ...
+  uint64_t *out_label;        // [qc][cap] ... and labels of the emitted entries, in no particular order
+};
+uint32_t flat_large_k_slice();         // entries one block of the histogram / emit launches covers
+uint32_t flat_large_k_dist_blocks();   // most row blocks of the distance launch (its waves stride over the row tiles)
+hipError_t launch_flat_large_k_distance(const FlatLargeKArgs &a, bool l2, bool bf16, int qb, hipStream_t s);
+hipError_t launch_flat_large_k_select(const FlatLargeKArgs &a, hipStream_t s);
+hipError_t launch_flat_large_k_emit(const FlatLargeKArgs &a, hipStream_t s);
+
 // node_mask.hip: n device filters translated into the graph's internal-id space in one launch.  d_items [n][kNodeMaskItemWords]
 // = {filter bits, nbits, dst} (device pointers); dst[i / 64] bit i % 64 = live bit i && label[i] < nbits && filter bit label[i],
 // every one of the (count + 63) / 64 words of dst is written (bits past count are 0); d_counts [n] (zeroed by the caller) += the

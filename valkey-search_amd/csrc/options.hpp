@@ -49,6 +49,8 @@ enum OptId : uint32_t {
   kOptShardThreads, kOptShardAllowStaged,
   // ---- batched pre-filter search -----------------------------------------------------------------------------------------
   kOptPrefilterDeviceResolve, kOptPrefilterLabelMapBytes,
+  // ---- FLAT k > 1024 in one row pass ---------------------------------------------------------------------------------------
+  kOptFlatLargeK, kOptFlatLargeKBytes,
   kOptCount
 };
 
@@ -126,6 +128,11 @@ inline const OptDesc &opt_desc(uint32_t id) {
       // point below the option-off median
       {"prefilter-device-resolve", nullptr, 0, 0, 1},
       {"prefilter-label-map-bytes", nullptr, (uint64_t)1 << 30, 0, kMax},         // ... most device memory an index's (a shard's) label map may hold; a map beyond it is not built: the host resolves
+      // FLAT k > 1024: one dense distance pass, a device select and a host finish (flat_large_k.hip) instead of k / 1024 scans of
+      // the table; read per call.  Ships off: it goes on by default only once scripts/flat_large_k_probe.py shows no point below
+      // the option-off median
+      {"flat-large-k", nullptr, 0, 0, 1},
+      {"flat-large-k-bytes", nullptr, (uint64_t)1 << 30, 0, kMax},                // ... most device memory a chunk's distances and hand-back may hold; a table whose ONE row of distances is beyond it takes the paged path
   };
   return t[id];
 }

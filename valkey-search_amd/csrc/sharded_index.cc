@@ -641,6 +641,22 @@ class ShardedIndex final : public Index {
     return Status::Ok();
   }
 
+  Status large_k_stats(vk_flat_large_k_stats *out) override {   // every shard serves its own large-k search: the sums
+    memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    for (auto &sh : shards_) {
+      vk_flat_large_k_stats t;
+      VK_TRY(sh->large_k_stats(&t));
+      out->queries += t.queries;
+      out->one_pass_queries += t.one_pass_queries;
+      out->fallback_queries += t.fallback_queries;
+      out->chunks += t.chunks;
+      out->emitted_entries += t.emitted_entries;
+      out->row_passes += t.row_passes;
+    }
+    return Status::Ok();
+  }
+
   Status distance(uint64_t label, const float *query, float *out) override {
     uint32_t s;
     if (!route_of(label, &s)) return Status::Err(VK_ERR_NOT_FOUND, "Couldn't find internal id");

@@ -787,6 +787,13 @@ int vk_index_filter_exact_stats(vk_index *ix, vk_filter_exact_stats *out) {
   return guarded([&] { return ix->impl->filter_exact_stats(out); });
 }
 
+int vk_index_large_k_stats(vk_index *ix, vk_flat_large_k_stats *out) {
+  if (!out) return fail(VK_ERR_INVALID, "out is NULL");
+  if (out->struct_size != sizeof(vk_flat_large_k_stats)) return fail(VK_ERR_INVALID, "vk_flat_large_k_stats.struct_size mismatch");
+  VK_NEED(ix);
+  return guarded([&] { return ix->impl->large_k_stats(out); });
+}
+
 int vk_index_filter_cache_get(vk_index *ix, const void *key, uint64_t key_len, uint64_t epoch, vk_filter **out) {
   VK_NEED(ix);
   if (!out || (key_len && !key)) return fail(VK_ERR_INVALID, "NULL argument");
