@@ -554,7 +554,8 @@ int vk_index_shard_stats(vk_index *ix, uint32_t shard, vk_index_stats *out);
  * filter passes of the most recent batch read instead of the f32 rows -- allocated rows x padded dim x 2 (summed over the
  * shards of a sharded index); 0 = that batch read the f32 rows (option off, L2 or bf16 index, no room on the device) or took
  * no filter pass.  A call of its own, so that vk_index_stats keeps its size; the image is counted in
- * vk_index_stats.device_bytes. */
+ * vk_index_stats.device_bytes.  Option flat-image-format picks the image's number format (0 = f16, 1 = bf16, 2 = bf16 for an
+ * index or shard of at least 1 250 000 rows, the default; read per batch): same size, same answers, another filter margin. */
 int vk_index_filter_image_bytes(vk_index *ix, uint64_t *out_bytes);
 /* HNSW node masks (options hnsw-node-mask, hnsw-node-mask-bytes).  A device filter is a bitmap over LABELS, the graph is
  * walked by INTERNAL ids: per (filter, graph) the index keeps one bit per published node, "live and allowed", built on the

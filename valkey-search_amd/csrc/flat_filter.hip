@@ -31,7 +31,15 @@
 // sum |x_i q_i| <= |x| |q| (Cauchy-Schwarz; tight exactly for the near neighbours that matter):
 //   |approx - dot_real| <= |x||q| (2^-11 + 2^-11 + 2^-22 + D 2^-22) + 2^-25 sqrt(D) (|x| + |q|) (1 + 2^-11)
 // and the reference's own f32 result differs from dot_real by at most (D/16 + 5) 2^-24 |x||q|, its 1 - dot by 2^-24
-// max(1, |dist|).  As a polynomial in the row norm R with per-query coefficients (flat_qprep_kernel): E_q(R) = c2 R^2 +
+// max(1, |dist|).
+// bf16 operands (kBfMma): u = 2^-8 per rounded element; bf16 carries the f32 exponent, so its subnormal term is 2^-134 (and as
+// much again should the matrix cores flush a subnormal operand) -- the f16 one, 2^-25, stays in the formula and covers it;
+// products of bf16 values are exact in f32.  A bf16 INDEX rounds the query only:
+// |x.q^ - x.q| <= u |x||q|.  f32 rows behind a bf16 IMAGE (FlatFilterArgs::img_bf16) round both operands:
+//   |x^.q^ - x.q| <= |x^ - x||q^| + |x||q^ - q| <= u (1 + u) |x||q| + u |x||q| = (2u + u^2) |x||q| = (2^-7 + 2^-16) |x||q|
+// (element-wise |x^_i - x_i| <= u |x_i|, |q^_i| <= (1 + u) |q_i|, then Cauchy-Schwarz), and the accumulation term is relative
+// to sum |x^_i q^_i| <= (1 + u)^2 |x||q|.  The margin is 8 times the f16 image's: the price of the cheaper instruction.
+// As a polynomial in the row norm R with per-query coefficients (flat_qprep_kernel): E_q(R) = c2 R^2 +
 // c1 R + c0 (c2 = 0 for the inner-product space); the margin is applied once for the witness rows behind L_q and once
 // for the row at the gate.  Because R is per TILE, one long row in an un-normalised index widens the gate of its own
 // 128 rows only (r02: of every row).
@@ -97,10 +105,13 @@ constexpr int kFAStride16 = 80;              // ... of the kernels that multiply
 // rows16 (optional, f32 rows in the inner-product space): the f16 image of the rows, [row][stride_e] -- every element rounded
 // to nearest even, the expression ws_rows_store applies on the way into LDS, so that the DMA row path over the image
 // multiplies exactly what the register path converts from the f32 rows.  The padding is written as it is read (zeros);
-// rows beyond hi are not written.
+// rows beyond hi are not written.  img_bf16 (option flat-image-format = 1): the image holds bf16 instead -- round to nearest
+// even by the integer expression flat_qprep_kernel applies to bf16 query fragments, (u + 0x7FFF + ((u >> 16) & 1)) >> 16 on the
+// f32 bits -- for the bf16 index's passes.  (A non-finite element may come out as any bits: its tile's norm is +inf, every
+// pair of the tile survives whatever the product is, and the sample takes no witness from it.)
 __global__ __launch_bounds__(256) void row_stats_kernel(const void *rows, uint32_t bf16, uint32_t l2, uint32_t stride_e, uint32_t chunks,
                                                         uint32_t lo, uint32_t hi, uint32_t *stats, uint32_t *tile_norm, uint32_t *hn16,
-                                                        _Float16 *rows16) {
+                                                        _Float16 *rows16, uint32_t img_bf16) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 3, rq = lane >> 2;
   const uint32_t total_waves = gridDim.x * 4, n_tiles = (hi - lo + kRowsPerWave - 1) / kRowsPerWave;
   float best_n2 = 0.f, best_abs = 0.f;
@@ -117,10 +128,19 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const void *rows, uint32
       bad = bad || !(x.x - x.x == 0.f) || !(x.y - x.y == 0.f) || !(x.z - x.z == 0.f) || !(x.w - x.w == 0.f);
       if (rows16 != nullptr && row < hi) {
         f16x4 h;
-        h[0] = (_Float16)x.x;
-        h[1] = (_Float16)x.y;
-        h[2] = (_Float16)x.z;
-        h[3] = (_Float16)x.w;
+        if (img_bf16) {
+          const float e[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            const uint32_t u = __float_as_uint(e[t]);
+            h[t] = __builtin_bit_cast(_Float16, (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16));
+          }
+        } else {
+          h[0] = (_Float16)x.x;
+          h[1] = (_Float16)x.y;
+          h[2] = (_Float16)x.z;
+          h[3] = (_Float16)x.w;
+        }
         *reinterpret_cast<f16x4 *>(rows16 + (size_t)row * stride_e + (c * 4 + j) * 4) = h;
       }
     }
@@ -181,14 +201,15 @@ __global__ __launch_bounds__(1024) void tile_cap_kernel(const uint32_t *tile_nor
 }
 
 hipError_t launch_row_stats(const void *rows, bool bf16, bool l2, uint32_t stride_e, uint32_t lo, uint32_t hi, uint32_t n_tiles,
-                            uint32_t *stats, uint32_t *tile_norm, uint32_t *hn16, void *rows16, hipStream_t s) {
+                            uint32_t *stats, uint32_t *tile_norm, uint32_t *hn16, void *rows16, hipStream_t s, uint32_t image_format) {
   if (rows16 != nullptr && bf16) return hipErrorInvalidValue;   // (bf16 rows are their own 16-bit stream)
+  if (image_format != kImageF16 && image_format != kImageBf16) return hipErrorInvalidValue;
   lo &= ~127u;                                            // whole tiles: a step of 16 rows never straddles two of them
   if (hi > lo) {
     const uint32_t tiles = (hi - lo + kRowsPerWave - 1) / kRowsPerWave;
     const uint32_t blocks = std::min<uint32_t>((tiles + 3) / 4, 2048);
     hipLaunchKernelGGL(row_stats_kernel, dim3(blocks), dim3(256), 0, s, rows, bf16 ? 1u : 0u, l2 ? 1u : 0u, stride_e, stride_e / 16, lo, hi,
-                       stats, tile_norm, hn16, static_cast<_Float16 *>(rows16));
+                       stats, tile_norm, hn16, static_cast<_Float16 *>(rows16), image_format == kImageBf16 ? 1u : 0u);
   }
   hipLaunchKernelGGL(tile_cap_kernel, dim3(1), dim3(1024), 0, s, tile_norm, n_tiles, stats);
   return hipGetLastError();
@@ -232,7 +253,7 @@ __global__ __launch_bounds__(64) void flat_qprep_kernel(FlatFilterArgs a) {
     const float4 u = reinterpret_cast<const float4 *>(src)[k8 * 2], v = reinterpret_cast<const float4 *>(src)[k8 * 2 + 1];
     const float e[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
     f16x8 h;
-    if (a.qbf16) {   // bf16 fragments (round to nearest even) for the bf16 matrix-core path over bf16 rows
+    if (a.qbf16) {   // bf16 fragments (round to nearest even) for the bf16 matrix-core path over bf16 rows (or the bf16 image of f32 rows)
 #pragma unroll
       for (int t = 0; t < 8; ++t) {
         const uint32_t u = __float_as_uint(e[t]);
@@ -261,7 +282,11 @@ __global__ __launch_bounds__(64) void flat_qprep_kernel(FlatFilterArgs a) {
     //  rounded to bf16 -- 8 significant bits, unit roundoff 2^-8 per element.  r03 had 2^-9 here: half the true bound,
     //  found by the margin audit on queries at bf16 rounding midpoints, tests/helpers/exp_margin_check.py: |approx - exact|
     //  reached 1.31 E)
-    const float rel = (a.qbf16 ? 0x1p-8f : a.bf16 ? 0x1p-11f : 0x1p-10f) + 0x1p-22f + D * 0x1p-22f + (D / 16.f + 5.f) * 0x1p-24f;
+    // (f32 rows behind a bf16 IMAGE, a.img_bf16: BOTH operands are rounded to bf16, u = 2^-8 each -- 2u + u^2, see the header.  The
+    //  row term is as large as the query term: leaving it out is r03's mistake again, half the bound.  The accumulation term is
+    //  relative to sum |x^_i q^_i| <= (1 + u)^2 |x||q|: 1.01 of it, which the 1.001 below would not cover at this u.)
+    const float rel = a.img_bf16 ? (0x1p-7f + 0x1p-16f) + 0x1p-22f + 1.01f * D * 0x1p-22f + (D / 16.f + 5.f) * 0x1p-24f
+                                 : (a.qbf16 ? 0x1p-8f : a.bf16 ? 0x1p-11f : 0x1p-10f) + 0x1p-22f + D * 0x1p-22f + (D / 16.f + 5.f) * 0x1p-24f;
     const float sub = 0x1.01p-25f * sqrtf(D);
     float c2 = 0.f, c1 = (qn * rel + sub + 0x1p-23f * qn) * 1.001f, c0 = (sub * qn + 0x1p-23f) * 1.001f;
     if (a.l2) {
@@ -1563,6 +1588,7 @@ hipError_t launch_flat_filter(const FlatFilterArgs &a, uint32_t blocks, hipStrea
                         : reinterpret_cast<const void *>(&flat_filter_sample_kernel<true, false>))
                 : (a.l2 ? reinterpret_cast<const void *>(&flat_filter_sample_kernel<false, true>)
                         : reinterpret_cast<const void *>(&flat_filter_sample_kernel<false, false>));
+  if (a.img_bf16 && !(a.bf16 && a.qbf16 && !a.l2 && a.rows16 == nullptr)) return hipErrorInvalidValue;   // (the image stands in for bf16 rows)
   if (a.qbf16) {
     if (!a.bf16 || a.l2) return hipErrorInvalidValue;
     fn = a.mode == 1 ? reinterpret_cast<const void *>(&flat_filter_bfmma_sample_kernel) : reinterpret_cast<const void *>(&flat_filter_bfmma_kernel);

@@ -1070,7 +1070,8 @@ class FlatIndex final : public Index {
       all = true;
     }
     const bool wrote = store_.take_written(&lo, &hi);
-    ensure_image(wrote, &all);
+    std::unique_lock<std::shared_mutex> image_hold;   // (a format flip: held until the rewritten image is on the device)
+    ensure_image(wrote, &all, &image_hold);
     if (wrote || all) {
       // The tile norms and the bad-tile count only ever grow (atomicMax): rows that were overwritten or removed leave their
       // old maxima behind -- valid bounds, but an index that once held long or non-finite rows would keep wide gates (or stay
@@ -1086,7 +1087,7 @@ class FlatIndex final : public Index {
       Status st = [&]() -> Status {
         VK_HIP_TRY(launch_row_stats(store_.d_rows(), store_.bf16(), l2(), store_.stride_f(), (uint32_t)lo, (uint32_t)hi,
                                     (uint32_t)((count_ + 127) / 128), d_rowstats_.as<uint32_t>(), d_tile_norm_.as<uint32_t>(),
-                                    l2() ? d_hn16_.as<uint32_t>() : nullptr, d_rows16_.p, store_.stream()));
+                                    l2() ? d_hn16_.as<uint32_t>() : nullptr, d_rows16_.p, store_.stream(), image_format_));
         uint32_t h[3] = {0, 0, 0};
         VK_HIP_TRY(hipMemcpyAsync(h, d_rowstats_.p, sizeof h, hipMemcpyDeviceToHost, store_.stream()));
         VK_HIP_TRY(hipStreamSynchronize(store_.stream()));
@@ -1107,10 +1108,24 @@ class FlatIndex final : public Index {
   // sized like the tile table, re-made whole after a re-allocation (*all).  It is optional: with the option off it is
   // released here, and when the device has no room for it the refusal is remembered until the next writer phase or growth
   // (no hipMalloc per search) and the batches are served from the f32 rows.  Called under stats_mu_.
-  void ensure_image(bool wrote, bool *all) {
+  // The image holds ONE number format, image_format_ (option flat-image-format, read per batch: f16 or bf16).  A batch that asks
+  // for the other one has the WHOLE image rewritten (*all -- the rows written since the last batch are not the only ones in
+  // the old format), under image_mu_: no batch is between reading the pointer and the format and enqueueing its passes, and the
+  // lock is handed back (*hold) and kept until the rewrite has finished on the device (ensure_row_stats waits for it), so no
+  // batch ever reads an image that is half one format and half the other.
+  void ensure_image(bool wrote, bool *all, std::unique_lock<std::shared_mutex> *hold) {
     const bool want = !store_.bf16() && !l2() && opt_.get(kOptFlatF16Image) != 0;
     const size_t need = want ? (size_t)(store_.alloc_rows() + RowStore::kRowSlack) * store_.stride_f() * 2 : 0;
     if (wrote || image_refused_rows_ != store_.alloc_rows()) image_refused_ = false;
+    const uint64_t fopt = opt_.get(kOptFlatImageFormat);   // (2: by size -- the smallest index the bf16 image was measured on)
+    const uint32_t fmt = (fopt == 1 || (fopt == 2 && count_ >= kImageBf16AutoRows)) ? kImageBf16 : kImageF16;
+    if (want && d_rows16_.p != nullptr && d_rows16_.cap >= need && fmt != image_format_) {
+      *hold = std::unique_lock<std::shared_mutex>(image_mu_);
+      (void)hipDeviceSynchronize();   // (the passes already enqueued, on whichever stream, still read the old format)
+      image_format_ = fmt;
+      *all = true;
+      return;
+    }
     if (d_rows16_.cap >= need && (want || d_rows16_.p == nullptr)) return;
     if (want && image_refused_) return;
     std::unique_lock<std::shared_mutex> lk(image_mu_);   // (no batch is between reading the pointer and enqueueing its passes)
@@ -1125,6 +1140,7 @@ class FlatIndex final : public Index {
       return;
     }
     image_bytes_.store(d_rows16_.cap, std::memory_order_relaxed);
+    image_format_ = fmt;
     *all = true;
   }
 
@@ -1217,6 +1233,14 @@ class FlatIndex final : public Index {
     std::shared_lock<std::shared_mutex> image_lk(image_mu_);
     f.rows16 = (!store_.bf16() && !l2() && !filter_experiment && !filter_dump_active() && opt_.get(kOptFlatF16Image) != 0) ? d_rows16_.p : nullptr;
     last_filter_image_bytes_.store(f.rows16 ? (uint64_t)store_.alloc_rows() * dp * 2 : 0, std::memory_order_relaxed);
+    // a bf16 image (option flat-image-format = 1; the format the image HOLDS decides, under the lock): the image stands in for the
+    // rows of a bf16 index in every filter pass, the sample included -- bf16 fragments, the bf16 matrix-core instruction, rows by
+    // DMA -- and qprep charges the rows' rounding (img_bf16).  Tile norms, the norm cap and the re-rank stay with the f32 rows.
+    if (f.rows16 != nullptr && image_format_ == kImageBf16) {
+      f.rows = f.rows16;
+      f.rows16 = nullptr;
+      f.bf16 = f.qbf16 = f.dma = f.img_bf16 = 1;
+    }
     f.labels = store_.d_labels();
     f.allow_bits = d_allow;
     f.allow_nbits = allow_nbits;
@@ -1465,6 +1489,7 @@ class FlatIndex final : public Index {
   DevBuf d_rowstats_, d_hn16_, d_tile_norm_;
   DevBuf d_rows16_;                             // the f16 image of the rows (ensure_image; written under stats_mu_ + image_mu_)
   std::shared_mutex image_mu_;
+  uint32_t image_format_ = kImageF16;           // number format the image holds (written under stats_mu_ + image_mu_, read under either)
   bool image_refused_ = false;                  // the device had no room for the image (under stats_mu_) ...
   uint64_t image_refused_rows_ = 0;             // ... at this size of the row table
   std::atomic<uint64_t> image_bytes_{0};        // device memory the image holds (vk_index_stats.device_bytes)

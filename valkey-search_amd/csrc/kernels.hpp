@@ -188,6 +188,9 @@ struct FlatFilterArgs {
   // filter-mfma-shape) -- f32 rows over the image or, with bdma, through registers; bf16 rows with qbf16 and dma.  Every other
   // kernel ignores it.
   uint32_t mfma16;
+  // `rows` is the bf16 IMAGE of an f32 index's rows (option flat-image-format = 1; bf16 = qbf16 = 1, every pass runs the bf16
+  // index's kernels over it): the rows were rounded too, and qprep's margin charges both roundings.  0: rows as stored.
+  uint32_t img_bf16;
 #ifdef VK_EXPERIMENTS
   // the -DVK_EXPERIMENTS build only (csrc/Makefile `experiments`): kernels whose answers are INVALID, for timing
   uint32_t timing;            // VK_FILTER_TIMING=1: the kernel variant with cycle counters per phase (f32 rows, IP only)
@@ -226,8 +229,12 @@ bool flat_filter_supported(uint32_t row_stride_f, uint64_t k, bool bf16, bool l2
 // stats: [0] largest |row|^2 (SQUARED, reported only), [1] largest |element| of the index (f32 bits), [2] tiles flagged +inf
 // so far, [3] the norm cap of the sample's witnesses: the NORM |row| (f32 bits, same unit as tile_norm) that 97 % of the finite
 // tiles stay below (recomputed over n_tiles tiles)
+// rows16 (f32 rows): the 16-bit image of the rows is written along, as f16 (image_format kImageF16) or bf16 (kImageBf16)
+constexpr uint32_t kImageF16 = 0, kImageBf16 = 1;   // (values 0 and 1 of option flat-image-format)
+constexpr uint64_t kImageBf16AutoRows = 1250000;    // (value 2: bf16 from this many rows on)
 hipError_t launch_row_stats(const void *rows, bool bf16, bool l2, uint32_t stride_e, uint32_t lo, uint32_t hi, uint32_t n_tiles,
-                            uint32_t *stats, uint32_t *tile_norm, uint32_t *hn16, void *rows16, hipStream_t s);
+                            uint32_t *stats, uint32_t *tile_norm, uint32_t *hn16, void *rows16, hipStream_t s,
+                            uint32_t image_format = kImageF16);
 hipError_t launch_flat_bound_select(const FlatBoundArgs &a, hipStream_t s);
 constexpr uint32_t kFilterMaxGroups = 16384;   // group bounds per query the selection holds in registers (8192 sample tiles)
 hipError_t launch_flat_qprep(const FlatFilterArgs &a, hipStream_t s);

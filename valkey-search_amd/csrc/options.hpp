@@ -37,7 +37,7 @@ enum OptId : uint32_t {
   kOptKernelTiming,         // 1 = HIP event pairs around the dominant kernel's launches (vk_index_stats.filter_kernel_ns)
   // ---- FLAT: kernel selection and the candidate filter (K4h) ------------------------------------------------------------
   kOptFlatFilter, kOptFilterMinQueries, kOptFilterMinRows, kOptFilterPrepassRows, kOptFilterCap, kOptFilterSpillChunks,
-  kOptFilterBDma, kOptFilterRowDma, kOptFilterBf16Mfma, kOptFlatForceScan, kOptFlatFusedRerank, kOptFilterSecondBound, kOptFilterTwoPass, kOptFilterTwoPassMinTiles, kOptFilterEarlyPermille, kOptFlatF16Image, kOptFilterMfmaShape,
+  kOptFilterBDma, kOptFilterRowDma, kOptFilterBf16Mfma, kOptFlatForceScan, kOptFlatFusedRerank, kOptFilterSecondBound, kOptFilterTwoPass, kOptFilterTwoPassMinTiles, kOptFilterEarlyPermille, kOptFlatF16Image, kOptFilterMfmaShape, kOptFlatImageFormat,
   kOptGemmLockstep, kOptGemmPrepassRows, kOptGemmContig, kOptScanMinNrp, kOptUploadParallel,
   // ---- HNSW ----------------------------------------------------------------------------------------------------------------
   kOptHnswStageAdds, kOptHnswStageMax,
@@ -91,6 +91,12 @@ inline const OptDesc &opt_desc(uint32_t id) {
       {"filter-early-permille", "VK_FILTER_EARLY_PERMILLE", 0, 0, 250},          // ... the early pass's share of the rows (0 = sqrt(sample / rows))
       {"flat-f16-image", "VK_FLAT_F16_IMAGE", 1, 0, 1},                           // f32 rows, IP / COSINE: the filter reads a resident f16 image of the rows (+50 % of the row table)
       {"filter-mfma-shape", "VK_FILTER_MFMA_SHAPE", 1, 0, 1},                     // final passes in the IP / COSINE space (f32 rows, bf16 rows by DMA): 0 = v_mfma 32x32x16, 1 = 16x16x32
+      // ... the image's number format: 0 = f16 (the f16 matrix-core instruction, rows and queries rounded to 11 bits), 1 = bf16 (the
+      // bf16 index's passes over the image, sample included: 8 bits, a margin eight times as wide, the cheaper instruction under
+      // the power cap), 2 = bf16 for an index (a shard) of at least kImageBf16AutoRows rows, f16 below.  Read per batch; a batch
+      // that needs the other format has the whole image rewritten first.  Ships 2: bf16 won at every size measured, 1.25M and 10M
+      // rows x 768; nothing smaller was measured, so nothing smaller changes
+      {"flat-image-format", "VK_FLAT_IMAGE_FORMAT", 2, 0, 2},
       {"gemm-lockstep", "VK_GEMM_LOCKSTEP", 1, 0, 64},
       {"gemm-prepass-rows", "VK_GEMM_PREPASS", 16384, 0, kMax},
       {"gemm-contig", "VK_GEMM_CONTIG", 1, 0, 1},
