@@ -158,6 +158,14 @@ class Algo {
     Check(vk_index_large_k_stats(ix_, &s));
     return s;
   }
+  // the device label map across write phases (vk_index_label_map_stats; option prefilter-label-map-upkeep = 1: touched labels
+  // applied on the device instead of a rebuild per phase)
+  vk_label_map_stats labelMapStats() const {
+    vk_label_map_stats s;
+    s.struct_size = sizeof(s);
+    Check(vk_index_label_map_stats(ix_, &s));
+    return s;
+  }
   void flush() { Check(vk_index_flush(ix_)); }                             // write -> read phase switch
   void setCoalescing(uint32_t max_batch, uint32_t max_wait_us) { Check(vk_index_set_coalescing(ix_, max_batch, max_wait_us)); }
   vk_index *handle() const { return ix_; }

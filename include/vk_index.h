@@ -502,6 +502,37 @@ typedef struct vk_flat_large_k_stats {
   uint64_t row_passes;         /* scans of the whole table: one per chunk, one per pass of the paged path */
 } vk_flat_large_k_stats;
 int vk_index_large_k_stats(vk_index *ix, vk_flat_large_k_stats *out);
+/* The device label map across write phases, in a struct of its own (vk_prefilter_stats_v2 keeps its size): set struct_size =
+ * sizeof(vk_label_map_stats) before the call.  The map (label -> row slot / internal id, used by vk_index_search_labels_batch
+ * with prefilter-device-resolve = 1 and always by vk_index_search_filter_exact_batch) is tagged with the publication it was
+ * built from.  With option prefilter-label-map-upkeep = 0 (the default) the first pre-filter batch behind a write phase rebuilds
+ * it from every published label.  With 1 the labels the phase touched -- at most prefilter-label-map-delta-max of them -- are
+ * applied to the table on the device: an erased label keeps its bucket with no slot (a dead entry), a new one claims a
+ * bucket.  The map is rebuilt all the same when the phase touched more than that or brought labels in without naming them
+ * (a load, a device bulk commit), when the keys in the table, dead ones included, would pass half its buckets, and when the
+ * counters an apply hands back do not add up to the index's live count (delta_mismatches: never served from).  A sharded index
+ * answers the sums of its shards (one map per shard). */
+typedef struct vk_label_map_stats {
+  uint64_t struct_size;
+  uint64_t builds;             /* builds of the whole table (vk_prefilter_stats_v2.label_map_builds) */
+  uint64_t delta_batches;      /* publications met by applying the touched labels instead */
+  uint64_t delta_records;      /* ... and the (label, slot) records sent for them */
+  uint64_t claimed;            /* records that took a new bucket */
+  uint64_t revived;            /* ... that gave a dead entry a slot again */
+  uint64_t killed;             /* ... that took a live entry's slot away */
+  uint64_t moved;              /* ... that changed a live entry's slot */
+  uint64_t dead_entries;       /* keys in the table now that answer "unknown" */
+  uint64_t used_entries;       /* keys in the table now, dead ones included */
+  uint64_t capacity;           /* buckets of the table now */
+  uint64_t delta_mismatches;   /* applies whose counters did not add up: rebuilt at once */
+  uint64_t rebuilds_forced;    /* builds with upkeep on because of the everything flag, the load factor or the delta limit */
+} vk_label_map_stats;
+int vk_index_label_map_stats(vk_index *ix, vk_label_map_stats *out);
+/* The label map of a plain index back on the host (tests, debugging, like vk_filter_read): flushes, brings the map up to date
+ * exactly as a pre-filter batch would, and writes its live (label, slot) pairs in no particular order.  *out_n = their number,
+ * whatever cap is; at most cap pairs are written.  VK_ERR_INVALID on a sharded index; VK_ERR_INTERNAL when the device has
+ * no room for the map. */
+int vk_index_label_map_read(vk_index *ix, uint64_t *out_labels, uint32_t *out_slots, uint64_t cap, uint64_t *out_n);
 /* Cache: filters of one index under a caller-chosen key (e.g. the predicate's canonical text, "@tag:{x}") and EPOCH -- any
  * counter that changes whenever the answer of the predicate may have changed (the module: the count of write phases of the
  * schema's time-sliced mutex, src/index_schema.cc:285-292; finer: a mutation counter of the attribute's own index).  get
@@ -529,7 +560,9 @@ int vk_index_search_batch_filter_handles(vk_index *ix, const void *queries, uint
  *   turns labels into row slots with a label map kept on the device -- built on first use, rebuilt whole after a flush that
  *   published a label, a count or a tombstone, released by vk_index_resize and by the value 0 -- instead of one host hash
  *   lookup per key; same answers, and a map that finds no room -- on the device, or within prefilter-label-map-bytes, 1 GiB --
- *   leaves the batch on the host's lookups), ...
+ *   leaves the batch on the host's lookups), prefilter-label-map-upkeep (0 / 1, read per batch, ships 0: behind a write phase
+ *   the labels it touched are applied to that map on the device instead of the rebuild; vk_label_map_stats),
+ *   prefilter-label-map-delta-max (1 .. 1 << 24, default 65 536: a phase that touched more labels has the map rebuilt), ...
  * A sharded index applies an option to itself and to every shard.  Unknown name or value out of range: VK_ERR_INVALID.
  * Options take effect for searches that START after the call; no search path reads the environment. */
 int vk_index_set_option(vk_index *ix, const char *name, uint64_t value);

@@ -92,6 +92,14 @@ class FlatLargeKStats(C.Structure):
                 ("chunks", C.c_uint64), ("emitted_entries", C.c_uint64), ("row_passes", C.c_uint64)]
 
 
+class LabelMapStats(C.Structure):
+    """vk_label_map_stats"""
+    _fields_ = [("struct_size", C.c_uint64), ("builds", C.c_uint64), ("delta_batches", C.c_uint64), ("delta_records", C.c_uint64),
+                ("claimed", C.c_uint64), ("revived", C.c_uint64), ("killed", C.c_uint64), ("moved", C.c_uint64),
+                ("dead_entries", C.c_uint64), ("used_entries", C.c_uint64), ("capacity", C.c_uint64),
+                ("delta_mismatches", C.c_uint64), ("rebuilds_forced", C.c_uint64)]
+
+
 class FilterDelta(C.Structure):
     """vk_filter_delta"""
     _fields_ = [("base", C.c_void_p), ("nbits", C.c_uint64), ("clear_labels", C.c_void_p), ("n_clear", C.c_uint64),
@@ -196,6 +204,8 @@ def lib() -> C.CDLL:
     L.vk_index_search_filter_exact_batch.argtypes = [vp, vp, u64, u64, vp, vp, vp, vp]
     L.vk_index_filter_exact_stats.argtypes = [vp, C.POINTER(FilterExactStats)]
     L.vk_index_large_k_stats.argtypes = [vp, C.POINTER(FlatLargeKStats)]
+    L.vk_index_label_map_stats.argtypes = [vp, C.POINTER(LabelMapStats)]
+    L.vk_index_label_map_read.argtypes = [vp, vp, vp, u64, u64p]
     L.vk_index_filter_cache_get.argtypes = [vp, C.c_char_p, u64, u64, C.POINTER(vp)]
     L.vk_index_filter_cache_put.argtypes = [vp, C.c_char_p, u64, u64, vp]
     L.vk_index_search_filter.argtypes = [vp, vp, u64, u64, vp, vp, i32, vp, vp, u64p]
@@ -625,6 +635,25 @@ class Index:
         s.struct_size = C.sizeof(FlatLargeKStats)
         _check(lib().vk_index_large_k_stats(self._h, C.byref(s)))
         return s
+
+    def label_map_stats(self) -> LabelMapStats:
+        """the device label map across write phases (vk_index_label_map_stats; option prefilter-label-map-upkeep)"""
+        s = LabelMapStats()
+        s.struct_size = C.sizeof(LabelMapStats)
+        _check(lib().vk_index_label_map_stats(self._h, C.byref(s)))
+        return s
+
+    def label_map_read(self):
+        """vk_index_label_map_read: the map brought up to date as a pre-filter batch would, then its live entries as
+        (labels u64 [n], slots u32 [n]), in no particular order (tests, debugging; a plain index only)"""
+        n = C.c_uint64()
+        _check(lib().vk_index_label_map_read(self._h, None, None, 0, C.byref(n)))
+        labels = np.empty(max(n.value, 1), np.uint64)
+        slots = np.empty(max(n.value, 1), np.uint32)
+        m = C.c_uint64()
+        _check(lib().vk_index_label_map_read(self._h, _ptr(labels), _ptr(slots), n.value, C.byref(m)))
+        assert m.value == n.value
+        return labels[:n.value], slots[:n.value]
 
     def prefilter_stats(self) -> PrefilterStats:
         """the counters of search_labels_batch (vk_index_prefilter_stats; a sharded index sums its shards)"""

@@ -287,6 +287,7 @@ class FlatIndex final : public Index {
         for (uint64_t l : run_labels) slot_of_.erase(l);
         count_ -= run_labels.size();
       }
+      label_map_.touched().touch_many(run_labels.data(), run_labels.size());   // (in the table, or given back: either way another answer)
       run_labels.clear();
       return s;
     };
@@ -313,11 +314,13 @@ class FlatIndex final : public Index {
     if (it == slot_of_.end()) return Status::Ok();  // bruteforce.h:95-98: silently ignored
     uint32_t cur = it->second;
     slot_of_.erase(it);
+    label_map_.touched().touch(label);
     uint32_t last = (uint32_t)count_ - 1;
     if (cur != last) {
       uint64_t moved = store_.host_labels()[last];
       slot_of_[moved] = cur;
       store_.stage_move(cur, last, moved);
+      label_map_.touched().touch(moved);   // (the row that fills the hole answers another slot from now on)
     }
     count_--;
     return Status::Ok();
@@ -334,6 +337,7 @@ class FlatIndex final : public Index {
   // prefilter-device-resolve = 0 releases the label map
   Status set_option(const char *name, uint64_t value) override {
     VK_TRY(opt_.set(name, value));
+    label_map_.touched().set_max(opt_.get(kOptPrefilterLabelMapDeltaMax));
     if (opt_.get(kOptPrefilterDeviceResolve) == 0 && label_map_.bytes() != 0) {
       std::unique_lock<std::shared_mutex> lk(rw_);
       (void)hipSetDevice(store_.device());
@@ -349,6 +353,20 @@ class FlatIndex final : public Index {
   void label_map_counters(uint64_t *builds, uint64_t *bytes) override {
     *builds = label_map_.builds();
     *bytes = label_map_.bytes();
+  }
+  Status label_map_stats(vk_label_map_stats *out) override {
+    label_map_.stats(out);
+    return Status::Ok();
+  }
+  // the map as the next pre-filter batch would find it, read back
+  Status label_map_read(uint64_t *out_labels, uint32_t *out_slots, uint64_t cap, uint64_t *out_n) override {
+    VK_TRY(flush_if_dirty());
+    std::shared_lock<std::shared_mutex> lk(rw_);
+    (void)hipSetDevice(store_.device());
+    CtxLease lease(pool_);
+    LabelMapTable map;
+    if (!label_map_ready(lease.ctx->stream, &map)) return Status::Err(VK_ERR_INTERNAL, "the device has no room for the label map");
+    return label_map_.read(out_labels, out_slots, cap, out_n);
   }
 
   Status set_ef(uint32_t) override { return Status::Ok(); }
@@ -515,9 +533,7 @@ class FlatIndex final : public Index {
     // and nothing is staged behind it, on the host otherwise
     bool on_device = false;
     LabelMapTable map;
-    if (opt_.get(kOptPrefilterDeviceResolve) != 0 && !store_.dirty() && count_ <= store_.alloc_rows() &&
-        label_map_.ready(store_.label_epoch(), (uint32_t)count_, store_.d_labels(), nullptr, 0, opt_.get(kOptPrefilterLabelMapBytes),
-                         lease.ctx->stream, &map)) {
+    if (opt_.get(kOptPrefilterDeviceResolve) != 0 && label_map_ready(lease.ctx->stream, &map)) {
       uint64_t resolved = 0;
       VK_TRY(prefilter_device_stage_keys(lease.ctx, map, store_.d_rows(), params_.dim, store_.stride_f(), l2(), store_.bf16(), queries, nq, k,
                                          labels, list_begin, n_labels, out, &on_device, &resolved));
@@ -553,9 +569,7 @@ class FlatIndex final : public Index {
     if (bits == nullptr) return Status::Err(VK_ERR_INVALID, "the filter has no copy on the index's device");
     CtxLease lease(pool_);
     LabelMapTable map;
-    const bool have = !store_.dirty() && count_ <= store_.alloc_rows() &&
-                      label_map_.ready(store_.label_epoch(), (uint32_t)count_, store_.d_labels(), nullptr, 0, opt_.get(kOptPrefilterLabelMapBytes),
-                                       lease.ctx->stream, &map);
+    const bool have = label_map_ready(lease.ctx->stream, &map);
     uint64_t expanded = 0, known = 0;
     VK_TRY(prefilter_handle_stage(lease.ctx, have ? &map : nullptr, bits, f.nbits(), f.allowed(), store_.d_rows(), params_.dim, store_.stride_f(),
                                   l2(), store_.bf16(), queries, nq, k, out, &expanded, &known));
@@ -640,6 +654,7 @@ class FlatIndex final : public Index {
       }
       store_.stage_label((uint32_t)i, lab);
     }
+    label_map_.touched().set_all();   // (labels that came in without passing add_locked)
     count_ = n;
     store_.note_written(0, n);   // (the caller filled the rows on the device)
     return store_.flush();
@@ -660,8 +675,26 @@ class FlatIndex final : public Index {
       slot = (uint32_t)count_++;
       slot_of_.emplace(label, slot);
       if (label > max_label_) max_label_ = label;
+      label_map_.touched().touch(label);
     }
     return store_.stage_write(slot, row, label);
+  }
+
+  // The device label map for this publication: built, or (option prefilter-label-map-upkeep) brought up to date from the
+  // labels the write phase touched.  Only with nothing staged behind the last flush -- so slot_of_, which the records are
+  // made from, is the published state.  The caller holds rw_ shared.
+  bool label_map_ready(hipStream_t s, LabelMapTable *map) {
+    if (store_.dirty() || count_ > store_.alloc_rows()) return false;
+    LabelMapUpkeep up;
+    up.on = opt_.get(kOptPrefilterLabelMapUpkeep) != 0;
+    up.delta_max = opt_.get(kOptPrefilterLabelMapDeltaMax);
+    up.live = count_;
+    up.truth = [this](uint64_t label) -> uint32_t {
+      auto it = slot_of_.find(label);
+      return it == slot_of_.end() ? kLabelMapNone : it->second;
+    };
+    return label_map_.ready(store_.label_epoch(), (uint32_t)count_, store_.d_labels(), nullptr, 0, opt_.get(kOptPrefilterLabelMapBytes), s, map,
+                            &up);
   }
 
   Status flush_if_dirty() {
@@ -1597,6 +1630,7 @@ Status FlatIndex::load_from(vk_read_chunk_fn fn, void *user) {
     VK_TRY(add_locked(lab, reinterpret_cast<const float *>(buf.data())));
     if (store_.staged_bytes() >= ((size_t)256 << 20)) VK_TRY(store_.flush());
   }
+  label_map_.touched().set_all();   // (a load brings every label in)
   return store_.flush();
 }
 

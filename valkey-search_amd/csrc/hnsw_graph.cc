@@ -308,6 +308,7 @@ Status HnswGraph::set_tombstone(uint32_t id) {   // markDeletedInternal
   __atomic_fetch_or(links0_mut(id), kDeleteFlag, __ATOMIC_RELAXED);   // (see set_list_count)
   num_deleted_ += 1;
   mark(id, 0);
+  touched_label(labels_[id]);
   if (allow_replace_deleted_) {
     std::lock_guard<std::mutex> lk(vacant_mu_);
     vacant_.insert(id);
@@ -320,6 +321,7 @@ Status HnswGraph::clear_tombstone(uint32_t id) {   // unmarkDeletedInternal
   __atomic_fetch_and(links0_mut(id), ~kDeleteFlag, __ATOMIC_RELAXED);
   num_deleted_ -= 1;
   mark(id, 0);
+  touched_label(labels_[id]);
   if (allow_replace_deleted_) {
     std::lock_guard<std::mutex> lk(vacant_mu_);
     vacant_.erase(id);
@@ -414,6 +416,7 @@ Status HnswGraph::insert(const float *new_row, uint64_t label, uint32_t *out_id)
     count_.fetch_add(1, std::memory_order_release);
     label_lookup_[label] = node;
     note_label(label);
+    touched_label(label);
   }
   *out_id = node;
 
@@ -481,6 +484,7 @@ Status HnswGraph::add(const float *new_row, uint64_t label, uint32_t *out_id) {
     label_lookup_.erase(old_label);
     label_lookup_[label] = slot;
     note_label(label);
+    touched_label(label);   // (the slot's old label was recorded when it was tombstoned)
   }
   VK_TRY(clear_tombstone(slot));
   *out_id = slot;
@@ -526,6 +530,7 @@ Status HnswGraph::bulk_register(const float *rows, const uint64_t *labels, size_
     mark(id, 0);
     label_lookup_[labels[i]] = id;
     note_label(labels[i]);
+    touched_label(labels[i]);
   }
   count_.fetch_add(n, std::memory_order_release);
   return Status::Ok();

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "host_dist.hpp"
+#include "label_map_delta_host.hpp"
 #include "row_store.hpp"
 
 namespace vk {
@@ -79,6 +80,13 @@ class HnswGraph {
     while (label > cur && !max_label_.compare_exchange_weak(cur, label, std::memory_order_relaxed)) {}
   }
   uint64_t host_bytes() const;
+  // the device label map's upkeep (label_map_delta_host.hpp): every label whose answer -- an id below the published count
+  // that carries no tombstone, or "unknown" -- may have changed is recorded in the owner's set: a new node, a tombstone set
+  // or cleared, a tombstoned slot taken over by a new label.  nullptr (a graph on its own) records nothing.
+  void set_touch_sink(LabelTouchSet *sink) { touch_sink_ = sink; }
+  void touched_label(uint64_t label) {
+    if (touch_sink_) touch_sink_->touch(label);
+  }
 
   // dirty tracking for the device mirror
   uint8_t take_dirty(uint32_t id) { return dirty_[id].exchange(0, std::memory_order_acq_rel); }
@@ -199,6 +207,7 @@ class HnswGraph {
   std::atomic<size_t> num_deleted_{0};
   std::atomic<uint64_t> slot_reuses_{0};
   std::atomic<uint64_t> max_label_{0};
+  LabelTouchSet *touch_sink_ = nullptr;
   size_t M_, maxM_, maxM0_, efC_, ef_ = 10;
   double mult_;
   int maxlevel_ = -1;

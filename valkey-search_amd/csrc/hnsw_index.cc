@@ -57,6 +57,7 @@ class HnswIndex final : public Index {
         graph_(std::make_unique<HnswGraph>(p.dim, p.metric == VK_METRIC_L2, p.initial_cap, p.m, p.ef_construction,
                                            p.random_seed, p.allow_replace_deleted != 0)) {
     graph_->set_ef(p.ef_runtime ? p.ef_runtime : 10);
+    graph_->set_touch_sink(&label_map_.touched());
   }
   ~HnswIndex() override {
     (void)hipSetDevice(store_.device());
@@ -532,10 +533,7 @@ class HnswIndex final : public Index {
     // labels the lookup below accepts.
     bool on_device = false;
     LabelMapTable map;
-    if (opt_.get(kOptPrefilterDeviceResolve) != 0 && !store_.dirty() && !graph_->any_dirty() && !links_stale_ &&
-        pub_.count <= store_.alloc_rows() &&
-        label_map_.ready(mask_epoch_, pub_.count, store_.d_labels(), pub_.count ? d_links0_.as<uint32_t>() : nullptr,
-                         (uint32_t)graph_->maxM0() + 1, opt_.get(kOptPrefilterLabelMapBytes), lease.ctx->stream, &map)) {
+    if (opt_.get(kOptPrefilterDeviceResolve) != 0 && label_map_ready(lease.ctx->stream, &map)) {
       uint64_t resolved = 0;
       VK_TRY(prefilter_device_stage_keys(lease.ctx, map, store_.d_rows(), params_.dim, store_.stride_f(), l2(), store_.bf16(), queries, nq, k,
                                          labels, list_begin, n_labels, out, &on_device, &resolved));
@@ -570,9 +568,7 @@ class HnswIndex final : public Index {
     if (bits == nullptr) return Status::Err(VK_ERR_INVALID, "the filter has no copy on the index's device");
     CtxLease lease(pool_);
     LabelMapTable map;
-    const bool have = !store_.dirty() && !graph_->any_dirty() && !links_stale_ && pub_.count <= store_.alloc_rows() &&
-                      label_map_.ready(mask_epoch_, pub_.count, store_.d_labels(), pub_.count ? d_links0_.as<uint32_t>() : nullptr,
-                                       (uint32_t)graph_->maxM0() + 1, opt_.get(kOptPrefilterLabelMapBytes), lease.ctx->stream, &map);
+    const bool have = label_map_ready(lease.ctx->stream, &map);
     uint64_t expanded = 0, known = 0;
     VK_TRY(prefilter_handle_stage(lease.ctx, have ? &map : nullptr, bits, f.nbits(), f.allowed(), store_.d_rows(), params_.dim, store_.stride_f(),
                                   l2(), store_.bf16(), queries, nq, k, out, &expanded, &known));
@@ -668,6 +664,7 @@ class HnswIndex final : public Index {
   // hnsw-node-mask = 0 releases the masks (searches in flight keep theirs until they are done)
   Status set_option(const char *name, uint64_t value) override {
     VK_TRY(opt_.set(name, value));
+    label_map_.touched().set_max(opt_.get(kOptPrefilterLabelMapDeltaMax));
     if (opt_.get(kOptHnswNodeMask) == 0) {
       (void)hipSetDevice(store_.device());
       masks_.clear();
@@ -687,6 +684,36 @@ class HnswIndex final : public Index {
   void label_map_counters(uint64_t *builds, uint64_t *bytes) override {
     *builds = label_map_.builds();
     *bytes = label_map_.bytes();
+  }
+  Status label_map_stats(vk_label_map_stats *out) override {
+    label_map_.stats(out);
+    return Status::Ok();
+  }
+  // the map as the next pre-filter batch would find it, read back
+  Status label_map_read(uint64_t *out_labels, uint32_t *out_slots, uint64_t cap, uint64_t *out_n) override {
+    VK_TRY(flush_if_dirty());
+    std::shared_lock<std::shared_mutex> lk(rw_);
+    (void)hipSetDevice(store_.device());
+    CtxLease lease(pool_);
+    LabelMapTable map;
+    if (!label_map_ready(lease.ctx->stream, &map)) return Status::Err(VK_ERR_INTERNAL, "the device has no room for the label map");
+    return label_map_.read(out_labels, out_slots, cap, out_n);
+  }
+  // The device label map for this publication: built, or (option prefilter-label-map-upkeep) brought up to date from the
+  // labels the write phase touched.  Only when the host graph holds nothing the device has not seen -- so the lookup the
+  // records are made from, the host resolve's own, answers the published state.  The caller holds rw_ shared.
+  bool label_map_ready(hipStream_t s, LabelMapTable *map) {
+    if (store_.dirty() || graph_->any_dirty() || links_stale_ || pub_.count > store_.alloc_rows()) return false;
+    LabelMapUpkeep up;
+    up.on = opt_.get(kOptPrefilterLabelMapUpkeep) != 0;
+    up.delta_max = opt_.get(kOptPrefilterLabelMapDeltaMax);
+    up.live = (uint64_t)pub_.count - pub_.deleted;
+    up.truth = [this](uint64_t label) -> uint32_t {
+      uint32_t id;
+      return graph_->lookup(label, &id) && id < pub_.count && !graph_->is_deleted(id) ? id : kLabelMapNone;
+    };
+    return label_map_.ready(mask_epoch_, pub_.count, store_.d_labels(), pub_.count ? d_links0_.as<uint32_t>() : nullptr,
+                            (uint32_t)graph_->maxM0() + 1, opt_.get(kOptPrefilterLabelMapBytes), s, map, &up);
   }
 
   Status node_mask_stats(vk_node_mask_stats *out) override {
@@ -1751,6 +1778,8 @@ Status HnswIndex::load_from(vk_read_chunk_fn fn, void *user) {
                                        f[13] ? f[13] : params_.ef_construction, params_.random_seed,
                                        params_.allow_replace_deleted != 0);
   graph_->set_ef(params_.ef_runtime ? params_.ef_runtime : 10);   // ef_runtime is not persisted (vector_hnsw.cc:159-160)
+  graph_->set_touch_sink(&label_map_.touched());
+  label_map_.touched().set_all();   // (a load brings every label in without naming it)
   if (buf.size() < sl0 + vec + 8 + slu * 64) buf.resize(sl0 + vec + 8 + slu * 64);
   for (uint32_t i = 0; i < cur; ++i) {
     if (fn(user, buf.data(), buf.size(), &len)) return Status::Err(VK_ERR_INTERNAL, "read_chunk failed");

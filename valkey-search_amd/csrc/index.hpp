@@ -10,6 +10,7 @@
 
 #include <atomic>
 #include <condition_variable>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <shared_mutex>
@@ -19,6 +20,7 @@
 #include "../../include/vk_index.h"
 #include "filter_set.hpp"
 #include "kernels.hpp"
+#include "label_map_delta_host.hpp"
 #include "options.hpp"
 #include "prefilter_handle_host.hpp"
 #include "prefilter_host.hpp"
@@ -47,26 +49,47 @@ struct PinBuf {
 // built from: the index's publication counter and published count.  A batch that finds another tag rebuilds it -- a flush
 // stands between the two, and a flush holds the index's lock exclusively, so no kernel of an earlier batch still reads the
 // table.  Callers hold the index's shared lock (ready) or its exclusive lock (release).
+// With option prefilter-label-map-upkeep = 1 (LabelMapUpkeep::on) a batch that finds another tag does not rebuild: the labels
+// the write phase touched (touched(), recorded by the index wherever a label's answer can change) are turned into records
+// against the index's own truth and applied on the device (label_map_apply_kernel); label_map_delta_host.hpp has the rules
+// for when a rebuild is due all the same, and the check of the counters behind every apply.
+struct LabelMapUpkeep {
+  bool on = false;
+  uint64_t delta_max = 65536;                   // option prefilter-label-map-delta-max
+  uint64_t live = 0;                            // labels the index answers under this publication (HNSW: without tombstones)
+  std::function<uint32_t(uint64_t)> truth;      // label -> its slot now, or kLabelMapNone: the host resolve's own lookup
+};
+
 class DeviceLabelMap {
  public:
-  ~DeviceLabelMap() { buf_.release(); }
+  ~DeviceLabelMap() { buf_.release(); delta_.release(); }
   // false = no map for this publication (no room on the device, or the build's failure word was not zero): the batch
   // resolves on the host.  links0 != nullptr: HNSW, tombstoned nodes stay out.
   // budget: most bytes the table may take (option prefilter-label-map-bytes); read when the map is (re)built
   bool ready(uint64_t epoch, uint32_t count, const uint64_t *d_labels, const uint32_t *d_links0, uint32_t l0_stride, uint64_t budget,
-             hipStream_t s, LabelMapTable *out);
-  void release();
+             hipStream_t s, LabelMapTable *out, const LabelMapUpkeep *up = nullptr);
+  void release();   // ... and the touched set cleared: the next build starts from the published labels
   uint64_t bytes() const { return bytes_.load(std::memory_order_relaxed); }
   uint64_t builds() const { return builds_.load(std::memory_order_relaxed); }
+  LabelTouchSet &touched() { return touched_; }
+  void stats(vk_label_map_stats *out);          // (struct_size is the caller's business)
+  // vk_index_label_map_read: the live (label, slot) pairs of the table as it stands (after ready())
+  Status read(uint64_t *out_labels, uint32_t *out_slots, uint64_t cap, uint64_t *out_n);
 
  private:
+  bool rebuild(uint64_t epoch, uint32_t count, const uint64_t *d_labels, const uint32_t *d_links0, uint32_t l0_stride, uint64_t budget,
+               hipStream_t s, uint64_t headroom);
   std::mutex mu_;
-  DevBuf buf_;
+  DevBuf buf_, delta_;                          // the table | the records of an apply launch
   LabelMapTable t_{};
   uint64_t epoch_ = 0;
   uint32_t count_ = 0;
   bool tagged_ = false, usable_ = false;
+  uint64_t used_ = 0, live_ = 0;                // keys in the table (dead ones included) | entries with a slot
+  LabelTouchSet touched_;
   std::atomic<uint64_t> bytes_{0}, builds_{0};
+  std::atomic<uint64_t> delta_batches_{0}, delta_records_{0}, claimed_{0}, revived_{0}, killed_{0}, moved_{0}, delta_mismatches_{0},
+      rebuilds_forced_{0};
 };
 
 // Results this small are written by the kernels straight into the pinned host buffers (hipHostMalloc memory is
@@ -237,6 +260,15 @@ class Index {
     memset(out, 0, sizeof(*out));
     out->struct_size = sizeof(*out);
     return Status::Ok();
+  }
+  // vk_index_label_map_stats (a sharded index sums its shards) / vk_index_label_map_read (a plain index only)
+  virtual Status label_map_stats(vk_label_map_stats *out) {
+    memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    return Status::Ok();
+  }
+  virtual Status label_map_read(uint64_t *, uint32_t *, uint64_t, uint64_t *) {
+    return Status::Err(VK_ERR_INVALID, "the label map is read from a plain index");
   }
   virtual void release_label_map() {}   // ... given back (a sharded index's resize: its shards' maps)
   // sharded index: its shards (vk_index_shard_device_rows / _commit_device_rows address one of them)

@@ -497,6 +497,21 @@ struct LabelMapResolveArgs {
 };
 uint32_t label_map_key_tiles(uint64_t keys);
 hipError_t launch_label_map_resolve(const LabelMapResolveArgs &a, hipStream_t s);
+// apply (option prefilter-label-map-upkeep): n records, labels[i] -> slots[i], kLabelMapNone = "unknown from now on"; every
+// label at most once per launch.  The failure word and the four counters are cleared on the stream first.  counters
+// [kLabelMapCounters]: keys claimed, values None -> slot, slot -> None, slot -> another slot.  The failure word counts the
+// empty key as a record and a probe run as long as the table.  A grid of at most kLabelMapApplyMaxBlocks blocks strides
+// over the records.
+enum : uint32_t { kLabelMapClaimed = 0, kLabelMapRevived = 1, kLabelMapKilled = 2, kLabelMapMoved = 3, kLabelMapCounters = 4 };
+constexpr uint64_t kLabelMapApplyMaxBlocks = 256;
+struct LabelMapApplyArgs {
+  LabelMapTable t;
+  const uint64_t *labels;   // [n]
+  const uint32_t *slots;    // [n]
+  uint32_t n;
+  unsigned int *counters;   // [kLabelMapCounters]
+};
+hipError_t launch_label_map_apply(const LabelMapApplyArgs &a, hipStream_t s);
 // the answer of an empty index / shard: out_n = 0, every entry (+inf, kNoLabel)
 // fused re-rank + selection of the candidate filter's survivors (k <= 64): one block per query writes the query's answer
 hipError_t launch_flat_rerank(const FlatScanArgs &a, const MergeArgs &m, bool l2, bool bf16, hipStream_t s);

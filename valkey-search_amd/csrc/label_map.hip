@@ -16,6 +16,12 @@
 //   label_map_compact_kernel   one block per key tile again: the known keys' slots, and their positions in the key array,
 //                              to their places -- a ballot and a prefix over the block's four waves, so the order is the
 //                              list's and duplicates stay
+//   label_map_apply_kernel     the map brought up to date after a write phase (option prefilter-label-map-upkeep): one record
+//                              (label, slot or kLabelMapNone) per thread, every label at most once per launch.  A key that is
+//                              there gets the new value -- an erase stores kLabelMapNone and LEAVES THE KEY, a dead entry, so
+//                              probe runs stay whole and label_map_find answers "unknown" from the value; a key that is not
+//                              claims the first empty bucket as the build does (an erase of it does nothing).  Four counters
+//                              (claimed, revived, killed, moved) beside the failure word tell the host what happened.
 //
 // The three resolve launches write what prefilter_device_stage builds on the host from prefilter_resolve's output; K8b
 // and K8c (prefilter_select.hip) read it as they read the host's.
@@ -152,6 +158,52 @@ __global__ __launch_bounds__(256) void label_map_compact_kernel(LabelMapResolveA
   }
 }
 
+// one record per thread, grid-stride: labels[i] now answers slots[i] (kLabelMapNone = unknown).  The host sends every label
+// at most once per launch, so no two threads ever write the same value word; two threads may still want the same EMPTY
+// bucket, which the build's compare-and-swap settles -- the loser probes on.  A key, once written, is never taken back (an
+// erased label keeps its bucket with the value kLabelMapNone), so a key read with a plain load is either still empty --
+// then the compare-and-swap decides -- or final.
+__global__ __launch_bounds__(256) void label_map_apply_kernel(LabelMapApplyArgs a) {
+  const uint64_t mask = a.t.capacity - 1;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += gridDim.x * blockDim.x) {
+    const uint64_t label = a.labels[i];
+    const uint32_t slot = a.slots[i];
+    if (label == kLabelMapEmpty) {
+      atomicAdd(a.t.fail, 1u);
+      continue;
+    }
+    uint64_t h = label_map_bucket(label, a.t.capacity);
+    bool done = false;
+    for (uint64_t p = 0; p < a.t.capacity; ++p) {
+      uint64_t k = a.t.keys[h];
+      if (k == kLabelMapEmpty) {
+        if (slot == kLabelMapNone) {   // the map never held it: nothing to erase
+          done = true;
+          break;
+        }
+        k = atomicCAS(reinterpret_cast<unsigned long long *>(a.t.keys + h), (unsigned long long)kLabelMapEmpty, (unsigned long long)label);
+        if (k == kLabelMapEmpty) {
+          a.t.vals[h] = slot;
+          atomicAdd(a.counters + kLabelMapClaimed, 1u);
+          done = true;
+          break;
+        }
+      }
+      if (k == label) {
+        const uint32_t old = a.t.vals[h];
+        a.t.vals[h] = slot;
+        if (old == kLabelMapNone && slot != kLabelMapNone) atomicAdd(a.counters + kLabelMapRevived, 1u);
+        else if (old != kLabelMapNone && slot == kLabelMapNone) atomicAdd(a.counters + kLabelMapKilled, 1u);
+        else if (old != slot) atomicAdd(a.counters + kLabelMapMoved, 1u);
+        done = true;
+        break;
+      }
+      h = (h + 1) & mask;
+    }
+    if (!done) atomicAdd(a.t.fail, 1u);   // a whole turn of the table without the key or a free bucket
+  }
+}
+
 }  // namespace
 
 uint32_t label_map_key_tiles(uint64_t keys) { return (uint32_t)((keys + kKeyTile - 1) / kKeyTile); }
@@ -180,6 +232,19 @@ hipError_t launch_label_map_resolve(const LabelMapResolveArgs &a, hipStream_t s)
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || a.n_ktiles == 0) return e;
   hipLaunchKernelGGL(label_map_compact_kernel, dim3(a.n_ktiles), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_label_map_apply(const LabelMapApplyArgs &a, hipStream_t s) {
+  if (a.t.capacity < kLabelMapMinCapacity || a.t.capacity > kLabelMapMaxCapacity || (a.t.capacity & (a.t.capacity - 1)) != 0)
+    return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(a.t.fail, 0, 4, s);
+  if (e != hipSuccess) return e;
+  e = hipMemsetAsync(a.counters, 0, kLabelMapCounters * 4, s);
+  if (e != hipSuccess || a.n == 0) return e;
+  const uint64_t want = ((uint64_t)a.n + 255) / 256;
+  const uint32_t blocks = (uint32_t)(want < kLabelMapApplyMaxBlocks ? want : kLabelMapApplyMaxBlocks);
+  hipLaunchKernelGGL(label_map_apply_kernel, dim3(blocks), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

@@ -51,6 +51,8 @@ enum OptId : uint32_t {
   kOptPrefilterDeviceResolve, kOptPrefilterLabelMapBytes,
   // ---- FLAT k > 1024 in one row pass ---------------------------------------------------------------------------------------
   kOptFlatLargeK, kOptFlatLargeKBytes,
+  // ---- the device label map kept up to date across write phases --------------------------------------------------------------
+  kOptPrefilterLabelMapUpkeep, kOptPrefilterLabelMapDeltaMax,
   kOptCount
 };
 
@@ -139,6 +141,11 @@ inline const OptDesc &opt_desc(uint32_t id) {
       // the option-off median
       {"flat-large-k", nullptr, 0, 0, 1},
       {"flat-large-k-bytes", nullptr, (uint64_t)1 << 30, 0, kMax},                // ... most device memory a chunk's distances and hand-back may hold; a table whose ONE row of distances is beyond it takes the paged path
+      // the device label map after a write phase: 1 = the labels the phase touched are applied to the table on the device
+      // (label_map_apply_kernel) instead of a rebuild from every published label; read per batch.  Ships off: it goes on by
+      // default only once scripts/label_map_upkeep_probe.py shows no point below the option-off median
+      {"prefilter-label-map-upkeep", nullptr, 0, 0, 1},
+      {"prefilter-label-map-delta-max", nullptr, 65536, 1, 1u << 24},             // ... most touched labels a write phase may leave; beyond it the map is rebuilt whole
   };
   return t[id];
 }

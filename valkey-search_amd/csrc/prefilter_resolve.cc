@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <vector>
 
 #include "index.hpp"
 #include "label_map_hash.hpp"
@@ -12,40 +13,118 @@
 namespace vk {
 
 // ---- the map of one index ---------------------------------------------------------------------------------------------
+// the table built whole from the published labels on stream s, the stream synchronised; headroom = slots beyond `count` the
+// sizing rule is asked for (upkeep: a table that is exactly twice the count would be due again after the first new label)
+bool DeviceLabelMap::rebuild(uint64_t epoch, uint32_t count, const uint64_t *d_labels, const uint32_t *d_links0, uint32_t l0_stride,
+                             uint64_t budget, hipStream_t s, uint64_t headroom) {
+  tagged_ = true;
+  epoch_ = epoch;
+  count_ = count;
+  usable_ = false;
+  used_ = live_ = 0;
+  const uint64_t capacity = label_map_capacity((uint64_t)count + headroom);
+  const uint64_t bytes = capacity * 12 + 32;   // keys | values | the failure word, the four counters of an apply launch
+  if (bytes > budget || capacity > kLabelMapMaxCapacity || !buf_.ensure(bytes).ok()) {
+    buf_.release();
+    bytes_.store(0, std::memory_order_relaxed);
+    return false;
+  }
+  bytes_.store(buf_.cap, std::memory_order_relaxed);
+  t_.keys = buf_.as<uint64_t>();
+  t_.vals = reinterpret_cast<uint32_t *>(t_.keys + capacity);
+  t_.fail = reinterpret_cast<unsigned int *>(t_.vals + capacity);
+  t_.capacity = capacity;
+  LabelMapBuildArgs a{};
+  a.t = t_;
+  a.labels = d_labels;
+  a.links0 = d_links0;
+  a.l0_stride = l0_stride;
+  a.count = count;
+  unsigned int failed = 1;
+  if (launch_label_map_build(a, s) != hipSuccess || hipMemcpyAsync(&failed, t_.fail, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  builds_.fetch_add(1, std::memory_order_relaxed);
+  usable_ = failed == 0;
+  return usable_;
+}
+
 bool DeviceLabelMap::ready(uint64_t epoch, uint32_t count, const uint64_t *d_labels, const uint32_t *d_links0, uint32_t l0_stride, uint64_t budget,
-                           hipStream_t s, LabelMapTable *out) {
+                           hipStream_t s, LabelMapTable *out, const LabelMapUpkeep *up) {
   std::lock_guard<std::mutex> g(mu_);
-  if (!tagged_ || epoch_ != epoch || count_ != count) {   // another publication: rebuilt whole, on this batch's stream
-    tagged_ = true;
-    epoch_ = epoch;
-    count_ = count;
-    usable_ = false;
-    const uint64_t capacity = label_map_capacity(count);
-    const uint64_t bytes = capacity * 12 + 16;   // keys | values | the failure word
-    if (bytes > budget || capacity > kLabelMapMaxCapacity || !buf_.ensure(bytes).ok()) {
-      buf_.release();
-      bytes_.store(0, std::memory_order_relaxed);
-      return false;
+  const bool same = tagged_ && epoch_ == epoch && count_ == count;
+  if (up == nullptr || !up->on) {
+    if (!same) {   // another publication: rebuilt whole, on this batch's stream
+      touched_.clear();   // (whatever the phase touched is in the labels the build reads)
+      rebuild(epoch, count, d_labels, d_links0, l0_stride, budget, s, 0);
+      used_ = live_ = up ? up->live : 0;
     }
-    bytes_.store(buf_.cap, std::memory_order_relaxed);
-    t_.keys = buf_.as<uint64_t>();
-    t_.vals = reinterpret_cast<uint32_t *>(t_.keys + capacity);
-    t_.fail = reinterpret_cast<unsigned int *>(t_.vals + capacity);
-    t_.capacity = capacity;
-    LabelMapBuildArgs a{};
-    a.t = t_;
-    a.labels = d_labels;
-    a.links0 = d_links0;
-    a.l0_stride = l0_stride;
-    a.count = count;
-    unsigned int failed = 1;
-    if (launch_label_map_build(a, s) != hipSuccess || hipMemcpyAsync(&failed, t_.fail, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-      (void)hipGetLastError();
-      return false;
+  } else if (!same || !touched_.empty()) {
+    // upkeep: the labels the write phase touched against the index's truth, applied to the table where it lies.  Everything
+    // up to the synchronise happens under mu_: no other stream sees a half-applied table.
+    std::vector<uint64_t> labels;
+    bool everything = false;
+    touched_.take(&labels, &everything);
+    LabelMapDelta d;
+    if (!everything && labels.size() > up->delta_max) everything = true;
+    if (!everything && tagged_ && usable_) label_map_net_delta(&labels, up->truth, &d);
+    LabelMapState st;
+    st.usable = tagged_ && usable_;
+    st.capacity = st.usable ? t_.capacity : 0;
+    st.used = used_;
+    st.live = live_;
+    const LabelMapPlan plan = label_map_plan(st, everything, d.upserts, count);
+    bool applied = false;
+    if (plan == LabelMapPlan::kApply) {
+      LabelMapApplied c;
+      const uint64_t n = d.labels.size();
+      bool ok = n <= 0xFFFFFFFFull && delta_.ensure(std::max<uint64_t>(n, 1) * 12).ok();
+      if (ok && n) {
+        LabelMapApplyArgs a{};
+        a.t = t_;
+        a.labels = delta_.as<uint64_t>();
+        a.slots = reinterpret_cast<const uint32_t *>(delta_.as<uint64_t>() + n);
+        a.n = (uint32_t)n;
+        a.counters = t_.fail + 1;
+        unsigned int back[1 + kLabelMapCounters] = {1, 0, 0, 0, 0};
+        ok = hipMemcpyAsync(delta_.p, d.labels.data(), n * 8, hipMemcpyHostToDevice, s) == hipSuccess &&
+             hipMemcpyAsync(delta_.as<uint64_t>() + n, d.slots.data(), n * 4, hipMemcpyHostToDevice, s) == hipSuccess &&
+             launch_label_map_apply(a, s) == hipSuccess &&
+             hipMemcpyAsync(back, t_.fail, sizeof(back), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+        if (!ok) (void)hipGetLastError();
+        c.fail = back[0];
+        c.claimed = back[1 + kLabelMapClaimed];
+        c.revived = back[1 + kLabelMapRevived];
+        c.killed = back[1 + kLabelMapKilled];
+        c.moved = back[1 + kLabelMapMoved];
+      }
+      uint64_t live_after = 0;
+      if (ok) {
+        delta_batches_.fetch_add(1, std::memory_order_relaxed);
+        delta_records_.fetch_add(n, std::memory_order_relaxed);
+        claimed_.fetch_add(c.claimed, std::memory_order_relaxed);
+        revived_.fetch_add(c.revived, std::memory_order_relaxed);
+        killed_.fetch_add(c.killed, std::memory_order_relaxed);
+        moved_.fetch_add(c.moved, std::memory_order_relaxed);
+        used_ += c.claimed;
+      }
+      if (ok && label_map_check_applied(live_, c, up->live, &live_after)) {
+        live_ = live_after;
+        epoch_ = epoch;
+        count_ = count;
+        applied = true;
+      } else {   // a touched label was missed somewhere, or a launch failed: never served from -- rebuilt at once, same stream
+        delta_mismatches_.fetch_add(1, std::memory_order_relaxed);
+      }
+    } else if (plan != LabelMapPlan::kRebuildNoMap) {
+      rebuilds_forced_.fetch_add(1, std::memory_order_relaxed);
     }
-    builds_.fetch_add(1, std::memory_order_relaxed);
-    usable_ = failed == 0;
+    if (!applied) {
+      rebuild(epoch, count, d_labels, d_links0, l0_stride, budget, s, count / 4);
+      used_ = live_ = up->live;
+    }
   }
   if (!usable_) return false;
   *out = t_;
@@ -55,8 +134,49 @@ bool DeviceLabelMap::ready(uint64_t epoch, uint32_t count, const uint64_t *d_lab
 void DeviceLabelMap::release() {
   std::lock_guard<std::mutex> g(mu_);
   buf_.release();
+  delta_.release();
   bytes_.store(0, std::memory_order_relaxed);
   tagged_ = usable_ = false;
+  used_ = live_ = 0;
+  touched_.clear();
+}
+
+void DeviceLabelMap::stats(vk_label_map_stats *out) {
+  std::lock_guard<std::mutex> g(mu_);
+  const bool have = tagged_ && usable_;
+  out->builds = builds_.load(std::memory_order_relaxed);
+  out->delta_batches = delta_batches_.load(std::memory_order_relaxed);
+  out->delta_records = delta_records_.load(std::memory_order_relaxed);
+  out->claimed = claimed_.load(std::memory_order_relaxed);
+  out->revived = revived_.load(std::memory_order_relaxed);
+  out->killed = killed_.load(std::memory_order_relaxed);
+  out->moved = moved_.load(std::memory_order_relaxed);
+  out->dead_entries = have ? used_ - live_ : 0;
+  out->used_entries = have ? used_ : 0;
+  out->capacity = have ? t_.capacity : 0;
+  out->delta_mismatches = delta_mismatches_.load(std::memory_order_relaxed);
+  out->rebuilds_forced = rebuilds_forced_.load(std::memory_order_relaxed);
+}
+
+Status DeviceLabelMap::read(uint64_t *out_labels, uint32_t *out_slots, uint64_t cap, uint64_t *out_n) {
+  std::lock_guard<std::mutex> g(mu_);
+  *out_n = 0;
+  if (!tagged_ || !usable_) return Status::Err(VK_ERR_INTERNAL, "the device has no room for the label map");
+  std::vector<uint64_t> keys(t_.capacity);
+  std::vector<uint32_t> vals(t_.capacity);
+  VK_HIP_TRY(hipMemcpy(keys.data(), t_.keys, t_.capacity * 8, hipMemcpyDeviceToHost));
+  VK_HIP_TRY(hipMemcpy(vals.data(), t_.vals, t_.capacity * 4, hipMemcpyDeviceToHost));
+  uint64_t n = 0;
+  for (uint64_t h = 0; h < t_.capacity; ++h) {
+    if (keys[h] == kLabelMapEmpty || vals[h] == kLabelMapNone) continue;
+    if (n < cap) {
+      out_labels[n] = keys[h];
+      out_slots[n] = vals[h];
+    }
+    ++n;
+  }
+  *out_n = n;
+  return Status::Ok();
 }
 
 // ---- the driver ---------------------------------------------------------------------------------------------------------

@@ -657,6 +657,29 @@ class ShardedIndex final : public Index {
     return Status::Ok();
   }
 
+  Status label_map_stats(vk_label_map_stats *out) override {   // one label map per shard: the sums
+    memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    for (auto &sh : shards_) {
+      vk_label_map_stats t;
+      memset(&t, 0, sizeof(t));
+      VK_TRY(sh->label_map_stats(&t));
+      out->builds += t.builds;
+      out->delta_batches += t.delta_batches;
+      out->delta_records += t.delta_records;
+      out->claimed += t.claimed;
+      out->revived += t.revived;
+      out->killed += t.killed;
+      out->moved += t.moved;
+      out->dead_entries += t.dead_entries;
+      out->used_entries += t.used_entries;
+      out->capacity += t.capacity;
+      out->delta_mismatches += t.delta_mismatches;
+      out->rebuilds_forced += t.rebuilds_forced;
+    }
+    return Status::Ok();
+  }
+
   Status distance(uint64_t label, const float *query, float *out) override {
     uint32_t s;
     if (!route_of(label, &s)) return Status::Err(VK_ERR_NOT_FOUND, "Couldn't find internal id");

@@ -794,6 +794,20 @@ int vk_index_large_k_stats(vk_index *ix, vk_flat_large_k_stats *out) {
   return guarded([&] { return ix->impl->large_k_stats(out); });
 }
 
+int vk_index_label_map_stats(vk_index *ix, vk_label_map_stats *out) {
+  if (!out) return fail(VK_ERR_INVALID, "out is NULL");
+  if (out->struct_size != sizeof(vk_label_map_stats)) return fail(VK_ERR_INVALID, "vk_label_map_stats.struct_size mismatch");
+  VK_NEED(ix);
+  return guarded([&] { return ix->impl->label_map_stats(out); });
+}
+
+int vk_index_label_map_read(vk_index *ix, uint64_t *out_labels, uint32_t *out_slots, uint64_t cap, uint64_t *out_n) {
+  VK_NEED(ix);
+  if (!out_n || (cap && (!out_labels || !out_slots))) return fail(VK_ERR_INVALID, "NULL argument");
+  *out_n = 0;
+  return guarded([&] { return ix->impl->label_map_read(out_labels, out_slots, cap, out_n); });
+}
+
 int vk_index_filter_cache_get(vk_index *ix, const void *key, uint64_t key_len, uint64_t epoch, vk_filter **out) {
   VK_NEED(ix);
   if (!out || (key_len && !key)) return fail(VK_ERR_INVALID, "NULL argument");
