@@ -1664,6 +1664,8 @@ hipError_t launch_flat_filter(const FlatFilterArgs &a, uint32_t blocks, hipStrea
 #endif
   hipError_t e = ensure_max_lds(fn);   // (above the 64 KB default)
   if (e != hipSuccess) return e;
+  e = ensure_scratch(fn, s);
+  if (e != hipSuccess) return e;
   FlatFilterArgs args = a;
   void *params[] = {&args};
   return hipLaunchKernel(fn, dim3(blocks), dim3(kWsThreads), params, lds, s);

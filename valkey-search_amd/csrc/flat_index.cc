@@ -100,6 +100,7 @@ SearchCtx::~SearchCtx() {
                     &d_fq16, &d_fthr, &d_fcnt, &d_fcand, &d_fspill, &d_fsmax, &d_fpart_d, &d_fpart_l, &d_allow_tab, &d_lk_dist, &d_lk_work})
     b->release();
   for (PinBuf *b : {&h_q, &h_out_d, &h_out_l, &h_out_n, &h_tmp, &h_idx, &h_cancel, &h_lk}) b->release();
+  scratch_forget(stream);
   if (stream) (void)hipStreamDestroy(stream);
 }
 

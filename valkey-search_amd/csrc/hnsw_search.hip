@@ -1071,6 +1071,7 @@ hipError_t launch_hnsw_search(const HnswSearchArgs &a, bool l2, bool bf16, int e
     hipError_t er = ensure_max_lds(f);
     if (er != hipSuccess) return er;
   }
+  if (hipError_t er = ensure_scratch(f, s); er != hipSuccess) return er;
   HnswSearchArgs args = a;
   void *params[] = {&args};
   return hipLaunchKernel(f, dim3(blocks), dim3(64 * hnsw_waves_per_block(a)), params, lds, s);

@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <mutex>
+#include <unordered_map>
+
 // A/B constants of the launchers: fixed in the product library; the -DVK_EXPERIMENTS build (csrc/Makefile `experiments`)
 // reads them from the environment once so that scripts/ can sweep them.
 #ifdef VK_EXPERIMENTS
@@ -19,6 +22,54 @@ namespace vk {
 // different (k, ef) lanes could interleave "set 80 KB / set 50 KB / launch 80 KB" and fail the launch.  It is
 // now raised ONCE per (function, device) to the whole 160 KB of a CU; what a launch may use is still what it asks for.
 hipError_t ensure_max_lds(const void *fn);
+
+// A kernel whose registers spill (hnsw_search.hip: 20 .. 120 B per lane; the candidate filter's final passes: 12 .. 24 B) needs
+// scratch memory, and the runtime takes that from device memory when it DISPATCHES the kernel, for the hardware queue behind the
+// stream.  On a device with no memory left the dispatch cannot be served: the queue is aborted, and with it every stream of the
+// process that shares it -- each later HIP call fails, whoever makes it.  A launch is therefore refused (hipErrorOutOfMemory,
+// like the allocation it stands for) while the device cannot hold the scratch of a full device's waves and the stream has not
+// yet taken a launch with that much of it; once it has, the queue keeps what it was given and the launch needs nothing more.
+// Called by the launchers of such kernels just before the launch; scratch_forget when a stream is destroyed.
+struct ScratchBook {
+  std::mutex mu;
+  std::unordered_map<const void *, uint32_t> per_lane;   // kernel function -> private segment, bytes per lane
+  std::unordered_map<hipStream_t, uint32_t> given;       // stream -> the largest private segment launched on it
+  static ScratchBook &instance() {
+    static ScratchBook b;
+    return b;
+  }
+};
+inline hipError_t ensure_scratch(const void *fn, hipStream_t s) {
+  ScratchBook &b = ScratchBook::instance();
+  std::lock_guard<std::mutex> lk(b.mu);
+  auto it = b.per_lane.find(fn);
+  if (it == b.per_lane.end()) {
+    hipFuncAttributes at{};
+    const hipError_t e = hipFuncGetAttributes(&at, fn);
+    if (e != hipSuccess) return e;
+    it = b.per_lane.emplace(fn, (uint32_t)at.localSizeBytes).first;
+  }
+  const uint32_t want = it->second;
+  if (want == 0) return hipSuccess;
+  uint32_t &have = b.given[s];
+  if (want <= have) return hipSuccess;
+  int dev = 0, cus = 0;
+  (void)hipGetDevice(&dev);
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  // every wave slot of the device (32 per CU) with its 64 lanes, and room for what other threads allocate meanwhile
+  const size_t need = (size_t)want * 64 * 32 * (size_t)(cus > 0 ? cus : 256) + ((size_t)32 << 20);
+  size_t free_b = 0, total_b = 0;
+  const hipError_t e = hipMemGetInfo(&free_b, &total_b);
+  if (e != hipSuccess) return e;
+  if (free_b < need) return hipErrorOutOfMemory;
+  have = want;
+  return hipSuccess;
+}
+inline void scratch_forget(hipStream_t s) {
+  ScratchBook &b = ScratchBook::instance();
+  std::lock_guard<std::mutex> lk(b.mu);
+  b.given.erase(s);
+}
 
 // K3: FLAT scan over rows [row_begin,row_end) for nq queries.
 struct FlatScanArgs {

@@ -84,6 +84,7 @@ struct MultiCtx {
       if (l.stream) (void)hipStreamSynchronize(l.stream);
       for (DevBuf *b : {&l.d_q, &l.d_allow, &l.d_out_d, &l.d_out_l, &l.d_out_n}) b->release();
       if (l.done) (void)hipEventDestroy(l.done);
+      scratch_forget(l.stream);
       if (l.stream) (void)hipStreamDestroy(l.stream);
     }
     for (GatherGroup &g : group) {
@@ -96,6 +97,7 @@ struct MultiCtx {
     for (PinBuf *b : {&h_q, &h_fin_d, &h_fin_l, &h_fin_n, &h_cancel}) b->release();
     if (ready) (void)hipEventDestroy(ready);
     if (busy) (void)hipEventDestroy(busy);
+    scratch_forget(s0);
     if (s0) (void)hipStreamDestroy(s0);
   }
 };
