@@ -158,6 +158,13 @@ class Algo {
     Check(vk_index_large_k_stats(ix_, &s));
     return s;
   }
+  // ... and of the device sort of their hand-back (vk_index_large_k_sort_stats; option flat-large-k-device-sort = 1)
+  vk_flat_large_k_sort_stats largeKSortStats() const {
+    vk_flat_large_k_sort_stats s;
+    s.struct_size = sizeof(s);
+    Check(vk_index_large_k_sort_stats(ix_, &s));
+    return s;
+  }
   // the device label map across write phases (vk_index_label_map_stats; option prefilter-label-map-upkeep = 1: touched labels
   // applied on the device instead of a rebuild per phase)
   vk_label_map_stats labelMapStats() const {

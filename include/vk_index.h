@@ -502,6 +502,24 @@ typedef struct vk_flat_large_k_stats {
   uint64_t row_passes;         /* scans of the whole table: one per chunk, one per pass of the paged path */
 } vk_flat_large_k_stats;
 int vk_index_large_k_stats(vk_index *ix, vk_flat_large_k_stats *out);
+/* The device sort of the one-pass path's hand-back, in a struct of its own (vk_flat_large_k_stats keeps its size): set
+ * struct_size = sizeof(vk_flat_large_k_sort_stats) before the call.  With options flat-large-k = 1 and
+ * flat-large-k-device-sort = 1 every query's emitted entries are ordered by (distance, label) on the device -- a merge sort
+ * behind the emit -- and only its first k entries are downloaded; with flat-large-k-device-sort = 0 (the default) the host
+ * downloads every slot of the hand-back and sorts it.  Both give the same bytes.  The three _ns fields grow only while option
+ * kernel-timing = 1, which makes the one-pass path wait for its launches before it starts the download.  An HNSW index
+ * answers zeros, a sharded index the sums of its shards. */
+typedef struct vk_flat_large_k_sort_stats {
+  uint64_t struct_size;
+  uint64_t sorted_queries;      /* queries answered from a device-ordered hand-back */
+  uint64_t merge_passes;        /* merge launches behind the tile sort, summed over chunks */
+  uint64_t downloaded_entries;  /* slots downloaded for sorted_queries: k each (emitted_entries goes on counting n) */
+  uint64_t timed_chunks;        /* chunks of the one-pass path run with kernel-timing = 1, the sort on or off */
+  uint64_t device_ns;           /* ... their launches, by a pair of events: distances, select, emit and the sort if on */
+  uint64_t download_ns;         /* ... their download, by the host's clock */
+  uint64_t finish_ns;           /* ... the host's loop over the hand-back (the sort, or the copy), by the host's clock */
+} vk_flat_large_k_sort_stats;
+int vk_index_large_k_sort_stats(vk_index *ix, vk_flat_large_k_sort_stats *out);
 /* The device label map across write phases, in a struct of its own (vk_prefilter_stats_v2 keeps its size): set struct_size =
  * sizeof(vk_label_map_stats) before the call.  The map (label -> row slot / internal id, used by vk_index_search_labels_batch
  * with prefilter-device-resolve = 1 and always by vk_index_search_filter_exact_batch) is tagged with the publication it was

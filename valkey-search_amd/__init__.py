@@ -92,6 +92,12 @@ class FlatLargeKStats(C.Structure):
                 ("chunks", C.c_uint64), ("emitted_entries", C.c_uint64), ("row_passes", C.c_uint64)]
 
 
+class FlatLargeKSortStats(C.Structure):
+    """vk_flat_large_k_sort_stats"""
+    _fields_ = [("struct_size", C.c_uint64), ("sorted_queries", C.c_uint64), ("merge_passes", C.c_uint64), ("downloaded_entries", C.c_uint64),
+                ("timed_chunks", C.c_uint64), ("device_ns", C.c_uint64), ("download_ns", C.c_uint64), ("finish_ns", C.c_uint64)]
+
+
 class LabelMapStats(C.Structure):
     """vk_label_map_stats"""
     _fields_ = [("struct_size", C.c_uint64), ("builds", C.c_uint64), ("delta_batches", C.c_uint64), ("delta_records", C.c_uint64),
@@ -204,6 +210,7 @@ def lib() -> C.CDLL:
     L.vk_index_search_filter_exact_batch.argtypes = [vp, vp, u64, u64, vp, vp, vp, vp]
     L.vk_index_filter_exact_stats.argtypes = [vp, C.POINTER(FilterExactStats)]
     L.vk_index_large_k_stats.argtypes = [vp, C.POINTER(FlatLargeKStats)]
+    L.vk_index_large_k_sort_stats.argtypes = [vp, C.POINTER(FlatLargeKSortStats)]
     L.vk_index_label_map_stats.argtypes = [vp, C.POINTER(LabelMapStats)]
     L.vk_index_label_map_read.argtypes = [vp, vp, vp, u64, u64p]
     L.vk_index_filter_cache_get.argtypes = [vp, C.c_char_p, u64, u64, C.POINTER(vp)]
@@ -634,6 +641,13 @@ class Index:
         s = FlatLargeKStats()
         s.struct_size = C.sizeof(FlatLargeKStats)
         _check(lib().vk_index_large_k_stats(self._h, C.byref(s)))
+        return s
+
+    def large_k_sort_stats(self) -> FlatLargeKSortStats:
+        """the device sort of the one-pass path's hand-back (vk_index_large_k_sort_stats; option flat-large-k-device-sort)"""
+        s = FlatLargeKSortStats()
+        s.struct_size = C.sizeof(FlatLargeKSortStats)
+        _check(lib().vk_index_large_k_sort_stats(self._h, C.byref(s)))
         return s
 
     def label_map_stats(self) -> LabelMapStats:

@@ -873,25 +873,46 @@ class FlatIndex final : public Index {
   // label) and cuts it at k -- the bytes search_in_passes returns.  A query flagged by the device (more ties at its k-th key
   // than the hand-back holds) is answered by search_in_passes afterwards, restricted to those queries; a table whose one row of
   // distances is beyond flat-large-k-bytes (or whose k is beyond 32-bit slots) goes there whole.  Cancellation: as the paged
-  // path, none.
+  // path, none.  With option flat-large-k-device-sort the sort kernels run behind the emit, the chunk plan counts their buffers,
+  // only the state words and k ordered entries per query come down, and the host copies them out -- the same bytes.
   Status search_large_k(SearchCtx *ctx, const SearchRequest &rq, uint64_t k, uint64_t count, const uint64_t *d_allow, float *out_dist,
                         uint64_t *out_label, uint64_t *out_n) {
     const uint64_t nq = rq.nq;
     const uint32_t chunks = store_.stride_f() / 16;
-    const LargeKPlan plan = large_k_plan(nq, count, k, opt_.get(kOptFlatLargeKBytes));
+    // option flat-large-k-device-sort: the merge sort behind the emit orders every hand-back, the download is the state words
+    // and the first k entries of every query, and the host's loop is a copy
+    const bool dsort = opt_.get(kOptFlatLargeKDeviceSort) != 0;
+    const bool timed = opt_.get(kOptKernelTiming) != 0;   // (vk_flat_large_k_sort_stats: where a chunk's time goes)
+    const LargeKPlan plan = dsort ? large_k_plan_sorted(nq, count, k, opt_.get(kOptFlatLargeKBytes)) : large_k_plan(nq, count, k, opt_.get(kOptFlatLargeKBytes));
     const uint64_t cap = large_k_cap(k);
     if (!plan.fits || cap > 0xFFFFFFFFull || count > 0xFFFFFFFFull || (size_t)chunks * 64 > 160 * 1024) {
       lk_.fallback_queries.fetch_add(nq, std::memory_order_relaxed);
       return search_in_passes(ctx, rq, k, count, d_allow, out_dist, out_label, out_n);
     }
-    const size_t per_q_back = (size_t)kLargeKStateWords * 4 + (size_t)cap * kLargeKSlotBytes;   // downloaded
+    const size_t back_slots = dsort ? (size_t)k : (size_t)cap;                                   // downloaded per query
+    const size_t per_q_back = (size_t)kLargeKStateWords * 4 + back_slots * kLargeKSlotBytes;
+    const size_t per_q_lists = dsort ? (size_t)large_k_sorted_list_bytes(k) : (size_t)cap * kLargeKSlotBytes;
+    const uint32_t passes = large_k_sort_passes(cap);
     VK_TRY(ctx->d_lk_dist.ensure((size_t)plan.chunk_q * plan.ld * 4));
-    VK_TRY(ctx->d_lk_work.ensure((size_t)plan.chunk_q * (per_q_back + (size_t)kLargeKBins * 4)));
+    VK_TRY(ctx->d_lk_work.ensure((size_t)plan.chunk_q * ((size_t)kLargeKStateWords * 4 + per_q_lists + (size_t)kLargeKBins * 4) + 32));
     VK_TRY(ctx->h_lk.ensure((size_t)plan.chunk_q * per_q_back));
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    struct EvGuard {
+      hipEvent_t &a, &b;
+      ~EvGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    } ev_guard{ev0, ev1};
+    if (timed) {
+      VK_HIP_TRY(hipEventCreate(&ev0));
+      VK_HIP_TRY(hipEventCreate(&ev1));
+    }
+    using Clock = std::chrono::steady_clock;
+    auto ns_since = [](Clock::time_point t) { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(Clock::now() - t).count(); };
     std::vector<uint64_t> redo;
     for (uint64_t q0 = 0; q0 < nq; q0 += plan.chunk_q) {
       const uint64_t qc = std::min<uint64_t>(plan.chunk_q, nq - q0);
-      // the chunk's block: [qc] state | [qc][cap] labels | [qc][cap] distance bits -- downloaded as one piece -- | [qc] histograms
+      // the chunk's block: [qc] state | [qc][cap] labels | [qc][cap] distance bits -- downloaded as one piece -- | [qc] histograms;
+      // with the device sort: [qc] state | [qc][k] labels | [qc][k] distance bits in order -- downloaded as one piece -- | the
+      // emit's [qc][cap] labels and bits | the merges' second pair of them | [qc] histograms (every part on an 8-byte boundary)
       char *w = ctx->d_lk_work.as<char>();
       FlatLargeKArgs a{};
       a.rows = store_.d_rows();
@@ -908,21 +929,56 @@ class FlatIndex final : public Index {
       a.ld = plan.ld;
       a.dist = ctx->d_lk_dist.as<float>();
       a.state = reinterpret_cast<uint32_t *>(w);
-      a.out_label = reinterpret_cast<uint64_t *>(w + qc * kLargeKStateWords * 4);
-      a.out_bits = reinterpret_cast<uint32_t *>(w + qc * kLargeKStateWords * 4 + qc * cap * 8);
-      a.hist = reinterpret_cast<uint32_t *>(w + qc * per_q_back);
+      FlatLargeKSortArgs sa{};
+      if (!dsort) {
+        a.out_label = reinterpret_cast<uint64_t *>(w + qc * kLargeKStateWords * 4);
+        a.out_bits = reinterpret_cast<uint32_t *>(w + qc * kLargeKStateWords * 4 + qc * cap * 8);
+        a.hist = reinterpret_cast<uint32_t *>(w + qc * per_q_back);
+      } else {
+        auto up8 = [](size_t x) { return (x + 7) & ~(size_t)7; };
+        const size_t lists = up8(qc * cap * kLargeKSlotBytes);
+        char *e = w + up8(qc * per_q_back);
+        sa.state = a.state;
+        sa.dense_label = reinterpret_cast<uint64_t *>(w + qc * kLargeKStateWords * 4);
+        sa.dense_bits = reinterpret_cast<uint32_t *>(w + qc * kLargeKStateWords * 4 + qc * k * 8);
+        sa.label = a.out_label = reinterpret_cast<uint64_t *>(e);
+        sa.bits = a.out_bits = reinterpret_cast<uint32_t *>(e + qc * cap * 8);
+        sa.label2 = reinterpret_cast<uint64_t *>(e + lists);
+        sa.bits2 = reinterpret_cast<uint32_t *>(e + lists + qc * cap * 8);
+        sa.qc = (uint32_t)qc;
+        sa.k = (uint32_t)k;
+        sa.cap = (uint32_t)cap;
+        a.hist = reinterpret_cast<uint32_t *>(e + 2 * lists);
+      }
       VK_HIP_TRY(hipMemsetAsync(a.hist, 0, qc * kLargeKBins * 4, ctx->stream));
+      if (timed) VK_HIP_TRY(hipEventRecord(ev0, ctx->stream));
       VK_HIP_TRY(launch_flat_large_k_distance(a, l2(), store_.bf16(), flat_scan_pick_qb(qc, chunks, 1, l2()), ctx->stream));
       VK_HIP_TRY(launch_flat_large_k_select(a, ctx->stream));
       VK_HIP_TRY(launch_flat_large_k_emit(a, ctx->stream));
+      if (dsort) VK_HIP_TRY(launch_flat_large_k_sort(sa, ctx->stream));
+      Clock::time_point t_down{};
+      if (timed) {   // the launches end before the download starts, so that each has a time of its own
+        VK_HIP_TRY(hipEventRecord(ev1, ctx->stream));
+        VK_HIP_TRY(hipEventSynchronize(ev1));
+        t_down = Clock::now();
+      }
       VK_HIP_TRY(hipMemcpyAsync(ctx->h_lk.p, w, qc * per_q_back, hipMemcpyDeviceToHost, ctx->stream));
       VK_HIP_TRY(hipStreamSynchronize(ctx->stream));
+      if (timed) {
+        float ms = 0;
+        lks_.download_ns.fetch_add(ns_since(t_down), std::memory_order_relaxed);
+        VK_HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+        lks_.device_ns.fetch_add((uint64_t)((double)ms * 1e6), std::memory_order_relaxed);
+        lks_.timed_chunks.fetch_add(1, std::memory_order_relaxed);
+      }
+      const Clock::time_point t_finish = Clock::now();
       lk_.chunks.fetch_add(1, std::memory_order_relaxed);
       lk_.row_passes.fetch_add(1, std::memory_order_relaxed);
+      if (dsort) lks_.merge_passes.fetch_add(passes, std::memory_order_relaxed);
       const char *h = ctx->h_lk.as<char>();
       const uint32_t *h_state = reinterpret_cast<const uint32_t *>(h);
       const uint64_t *h_label = reinterpret_cast<const uint64_t *>(h + qc * kLargeKStateWords * 4);
-      const uint32_t *h_bits = reinterpret_cast<const uint32_t *>(h + qc * kLargeKStateWords * 4 + qc * cap * 8);
+      const uint32_t *h_bits = reinterpret_cast<const uint32_t *>(h + qc * kLargeKStateWords * 4 + qc * back_slots * 8);
       uint64_t emitted = 0, served = 0;
       for (uint64_t q = 0; q < qc; ++q) {
         const uint32_t *st = h_state + q * kLargeKStateWords;   // T | k left | n_less | n_eq | n_real | counter | flag | 0
@@ -932,12 +988,24 @@ class FlatIndex final : public Index {
         }
         const uint64_t n = (uint64_t)st[2] + st[3];
         if (n > cap || st[5] != n) return Status::Err(VK_ERR_INTERNAL, "flat-large-k: the emit count does not match the select");
-        out_n[q0 + q] = large_k_finish(h_bits + q * cap, h_label + q * cap, n, k, out_dist + (q0 + q) * rq.k, out_label + (q0 + q) * rq.k);
+        if (dsort) {   // in order already: the first min(k, n) entries of the query's k dense slots
+          const uint64_t m = std::min<uint64_t>(k, n);
+          memcpy(out_dist + (q0 + q) * rq.k, h_bits + q * k, (size_t)m * 4);
+          memcpy(out_label + (q0 + q) * rq.k, h_label + q * k, (size_t)m * 8);
+          out_n[q0 + q] = m;
+        } else {
+          out_n[q0 + q] = large_k_finish(h_bits + q * cap, h_label + q * cap, n, k, out_dist + (q0 + q) * rq.k, out_label + (q0 + q) * rq.k);
+        }
         emitted += n;
         ++served;
       }
+      if (timed) lks_.finish_ns.fetch_add(ns_since(t_finish), std::memory_order_relaxed);
       lk_.emitted_entries.fetch_add(emitted, std::memory_order_relaxed);
       lk_.one_pass_queries.fetch_add(served, std::memory_order_relaxed);
+      if (dsort) {
+        lks_.sorted_queries.fetch_add(served, std::memory_order_relaxed);
+        lks_.downloaded_entries.fetch_add(served * k, std::memory_order_relaxed);
+      }
     }
     if (redo.empty()) return Status::Ok();
     // the flagged queries through the paged path: their vectors take the front of the query block, their answers come back
@@ -971,6 +1039,19 @@ class FlatIndex final : public Index {
     out->chunks = lk_.chunks.load(std::memory_order_relaxed);
     out->emitted_entries = lk_.emitted_entries.load(std::memory_order_relaxed);
     out->row_passes = lk_.row_passes.load(std::memory_order_relaxed);
+    return Status::Ok();
+  }
+
+  Status large_k_sort_stats(vk_flat_large_k_sort_stats *out) override {
+    memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    out->sorted_queries = lks_.sorted_queries.load(std::memory_order_relaxed);
+    out->merge_passes = lks_.merge_passes.load(std::memory_order_relaxed);
+    out->downloaded_entries = lks_.downloaded_entries.load(std::memory_order_relaxed);
+    out->timed_chunks = lks_.timed_chunks.load(std::memory_order_relaxed);
+    out->device_ns = lks_.device_ns.load(std::memory_order_relaxed);
+    out->download_ns = lks_.download_ns.load(std::memory_order_relaxed);
+    out->finish_ns = lks_.finish_ns.load(std::memory_order_relaxed);
     return Status::Ok();
   }
 
@@ -1541,6 +1622,10 @@ class FlatIndex final : public Index {
   struct LargeKCounters {
     std::atomic<uint64_t> queries{0}, one_pass_queries{0}, fallback_queries{0}, chunks{0}, emitted_entries{0}, row_passes{0};
   } lk_;
+  // ... and of the device sort of their hand-back (vk_flat_large_k_sort_stats)
+  struct LargeKSortCounters {
+    std::atomic<uint64_t> sorted_queries{0}, merge_passes{0}, downloaded_entries{0}, timed_chunks{0}, device_ns{0}, download_ns{0}, finish_ns{0};
+  } lks_;
   // per-call lower bounds of search_in_passes (set only around its scan() calls, under the ctx lease)
   static thread_local const float *lb_dist_;
   static thread_local const uint64_t *lb_label_;

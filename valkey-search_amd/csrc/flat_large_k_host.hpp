@@ -34,18 +34,39 @@ struct LargeKPlan {
   uint64_t chunk_q = 0;   // queries per chunk (the last chunk may hold fewer)
   uint64_t chunks = 0;
 };
-inline LargeKPlan large_k_plan(uint64_t nq, uint64_t count, uint64_t k, uint64_t budget_bytes) {
+// (list_bytes: what one query's lists take on the device next to its row of distances)
+inline LargeKPlan large_k_plan_lists(uint64_t nq, uint64_t count, uint64_t list_bytes, uint64_t budget_bytes) {
   LargeKPlan p;
   p.ld = (count + 63) & ~(uint64_t)63;
   if (nq == 0 || count == 0 || p.ld * 4 > budget_bytes) return p;
   p.fits = true;
-  const uint64_t per_q = p.ld * 4 + large_k_cap(k) * kLargeKSlotBytes;
+  const uint64_t per_q = p.ld * 4 + list_bytes;
   uint64_t c = std::max<uint64_t>(1, budget_bytes / per_q);
   c = std::min(c, std::min(nq, kLargeKMaxChunkQueries));
   if (c >= 8) c &= ~(uint64_t)7;
   p.chunk_q = c;
   p.chunks = (nq + c - 1) / c;
   return p;
+}
+inline LargeKPlan large_k_plan(uint64_t nq, uint64_t count, uint64_t k, uint64_t budget_bytes) {
+  return large_k_plan_lists(nq, count, large_k_cap(k) * kLargeKSlotBytes, budget_bytes);
+}
+
+// ---- the device sort of the hand-back (option flat-large-k-device-sort; the kernels behind the emit in flat_large_k.hip) ----
+// entries one block sorts in LDS (the slice of the histogram / emit launches); the merge passes work in blocks of as many outputs
+constexpr uint64_t kLargeKSortTile = 4096;
+// merge launches behind the tile sort: the host knows cap, not a query's n, so the runs double until one spans cap
+inline uint32_t large_k_sort_passes(uint64_t cap) {
+  const uint64_t tiles = (cap + kLargeKSortTile - 1) / kLargeKSortTile;
+  uint32_t p = 0;
+  while (((uint64_t)1 << p) < tiles) ++p;
+  return p;
+}
+// device bytes of one query's lists with the sort on: the emit's slots, the merges' second side, the dense hand-back
+inline uint64_t large_k_sorted_list_bytes(uint64_t k) { return (2 * large_k_cap(k) + k) * kLargeKSlotBytes; }
+// large_k_plan with those bytes per query instead of the one list (same rules otherwise)
+inline LargeKPlan large_k_plan_sorted(uint64_t nq, uint64_t count, uint64_t k, uint64_t budget_bytes) {
+  return large_k_plan_lists(nq, count, large_k_sorted_list_bytes(k), budget_bytes);
 }
 
 // order-preserving u32 of a non-NaN float, -0 and +0 sharing a key: merge_key of flat_scan.hip

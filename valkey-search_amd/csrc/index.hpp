@@ -261,6 +261,12 @@ class Index {
     out->struct_size = sizeof(*out);
     return Status::Ok();
   }
+  // vk_index_large_k_sort_stats (as large_k_stats)
+  virtual Status large_k_sort_stats(vk_flat_large_k_sort_stats *out) {
+    memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    return Status::Ok();
+  }
   // vk_index_label_map_stats (a sharded index sums its shards) / vk_index_label_map_read (a plain index only)
   virtual Status label_map_stats(vk_label_map_stats *out) {
     memset(out, 0, sizeof(*out));

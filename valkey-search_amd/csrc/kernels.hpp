@@ -637,6 +637,22 @@ uint32_t flat_large_k_dist_blocks();   // most row blocks of the distance launch
 hipError_t launch_flat_large_k_distance(const FlatLargeKArgs &a, bool l2, bool bf16, int qb, hipStream_t s);
 hipError_t launch_flat_large_k_select(const FlatLargeKArgs &a, hipStream_t s);
 hipError_t launch_flat_large_k_emit(const FlatLargeKArgs &a, hipStream_t s);
+// ... and behind the emit (option flat-large-k-device-sort): every query's n = n_less + n_eq emitted entries ordered by
+// (merge_key(distance bits), label) -- large_k_finish's order -- by a segmented merge sort: tiles of kLargeKSortTile entries
+// sorted in LDS, in place, then large_k_sort_passes(cap) merge launches between the emit's buffers and a second pair.  The
+// last launch writes entries [0, min(k, n)) of every query into the dense hand-back instead.  A flagged query (state word 6)
+// is not touched, nothing at or beyond n is read or written, the state words are only read.
+struct FlatLargeKSortArgs {
+  const uint32_t *state;      // [qc][kLargeKStateWords] as the select and the emit left them
+  uint32_t *bits;             // [qc][cap] the emit's distance bits ...
+  uint64_t *label;            // [qc][cap] ... and labels: tile-sorted in place, then one side of the merges
+  uint32_t *bits2;            // [qc][cap] the other side (may be null when large_k_sort_passes(cap) == 0)
+  uint64_t *label2;
+  uint32_t *dense_bits;       // [qc][k] the first min(k, n) distance bits in order ...
+  uint64_t *dense_label;      // [qc][k] ... and their labels
+  uint32_t qc, k, cap;        // qc <= 65535, k >= 1, cap >= 1
+};
+hipError_t launch_flat_large_k_sort(const FlatLargeKSortArgs &a, hipStream_t s);
 
 // node_mask.hip: n device filters translated into the graph's internal-id space in one launch.  d_items [n][kNodeMaskItemWords]
 // = {filter bits, nbits, dst} (device pointers); dst[i / 64] bit i % 64 = live bit i && label[i] < nbits && filter bit label[i],

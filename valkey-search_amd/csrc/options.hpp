@@ -53,6 +53,8 @@ enum OptId : uint32_t {
   kOptFlatLargeK, kOptFlatLargeKBytes,
   // ---- the device label map kept up to date across write phases --------------------------------------------------------------
   kOptPrefilterLabelMapUpkeep, kOptPrefilterLabelMapDeltaMax,
+  // ---- FLAT k > 1024 in one row pass: the hand-back ordered on the device ------------------------------------------------------
+  kOptFlatLargeKDeviceSort,
   kOptCount
 };
 
@@ -146,6 +148,11 @@ inline const OptDesc &opt_desc(uint32_t id) {
       // default only once scripts/label_map_upkeep_probe.py shows no point below the option-off median
       {"prefilter-label-map-upkeep", nullptr, 0, 0, 1},
       {"prefilter-label-map-delta-max", nullptr, 65536, 1, 1u << 24},             // ... most touched labels a write phase may leave; beyond it the map is rebuilt whole
+      // flat-large-k = 1: every query's hand-back is ordered by (distance, label) on the device (the merge sort behind the emit
+      // in flat_large_k.hip) and only its first k entries are downloaded, instead of a download of every slot and a host sort;
+      // read per call, nothing changes while flat-large-k is 0.  Ships off: it goes on by default only once
+      // scripts/flat_large_k_probe.py shows no point below the host-sort median
+      {"flat-large-k-device-sort", nullptr, 0, 0, 1},
   };
   return t[id];
 }

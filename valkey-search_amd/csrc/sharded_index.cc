@@ -659,6 +659,23 @@ class ShardedIndex final : public Index {
     return Status::Ok();
   }
 
+  Status large_k_sort_stats(vk_flat_large_k_sort_stats *out) override {   // ... and its own device sort: the sums
+    memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    for (auto &sh : shards_) {
+      vk_flat_large_k_sort_stats t;
+      VK_TRY(sh->large_k_sort_stats(&t));
+      out->sorted_queries += t.sorted_queries;
+      out->merge_passes += t.merge_passes;
+      out->downloaded_entries += t.downloaded_entries;
+      out->timed_chunks += t.timed_chunks;
+      out->device_ns += t.device_ns;
+      out->download_ns += t.download_ns;
+      out->finish_ns += t.finish_ns;
+    }
+    return Status::Ok();
+  }
+
   Status label_map_stats(vk_label_map_stats *out) override {   // one label map per shard: the sums
     memset(out, 0, sizeof(*out));
     out->struct_size = sizeof(*out);
