@@ -601,10 +601,10 @@ int vk_index_shard_count(vk_index *ix, uint32_t *out_n);
 /* the statistics of ONE shard (vk_index_get_stats of a sharded index sums the shards' cumulative counters; a per-shard
  * rate -- the slowest shard's kernel time per launch -- needs the shards' own deltas) */
 int vk_index_shard_stats(vk_index *ix, uint32_t shard, vk_index_stats *out);
-/* FLAT, f32 rows in the inner-product space (option flat-f16-image): bytes of the resident f16 image of the rows that the
- * filter passes of the most recent batch read instead of the f32 rows -- allocated rows x padded dim x 2 (summed over the
- * shards of a sharded index); 0 = that batch read the f32 rows (option off, L2 or bf16 index, no room on the device) or took
- * no filter pass.  A call of its own, so that vk_index_stats keeps its size; the image is counted in
+/* FLAT, f32 rows (inner-product space: option flat-f16-image; L2: option flat-l2-image, off by default, always f16): bytes of
+ * the resident f16 image of the rows that the filter passes of the most recent batch read instead of the f32 rows -- allocated
+ * rows x padded dim x 2 (summed over the shards of a sharded index); 0 = that batch read the f32 rows (option off, bf16 index,
+ * no room on the device) or took no filter pass.  A call of its own, so that vk_index_stats keeps its size; the image is counted in
  * vk_index_stats.device_bytes.  Option flat-image-format picks the image's number format (0 = f16, 1 = bf16, 2 = bf16 for an
  * index or shard of at least 1 250 000 rows, the default; read per batch): same size, same answers, another filter margin. */
 int vk_index_filter_image_bytes(vk_index *ix, uint64_t *out_bytes);

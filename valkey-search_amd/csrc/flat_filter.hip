@@ -102,7 +102,7 @@ constexpr int kFAStride16 = 80;              // ... of the kernels that multiply
 // valid bounds when rows are overwritten or removed.
 // hn16 (optional, L2 indexes): per row half its squared norm, split into two f16 (hi | lo << 16) -- the extra K-step
 // that turns the filter's dot product into dot - |x|^2 / 2.
-// rows16 (optional, f32 rows in the inner-product space): the f16 image of the rows, [row][stride_e] -- every element rounded
+// rows16 (optional, f32 rows; L2 indexes under option flat-l2-image, beside hn16): the f16 image of the rows, [row][stride_e] -- every element rounded
 // to nearest even, the expression ws_rows_store applies on the way into LDS, so that the DMA row path over the image
 // multiplies exactly what the register path converts from the f32 rows.  The padding is written as it is read (zeros);
 // rows beyond hi are not written.  img_bf16 (option flat-image-format = 1): the image holds bf16 instead -- round to nearest
@@ -907,7 +907,8 @@ __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
   static_assert(!kM16 || kDma || !kBf16, "16x16x32 with the rows through registers: f32 rows");
   constexpr int kAStride = kM16 ? kFAStride16 : kFAStride;
   static_assert(!kBDma || (!kDma && !kTiming && !kSample && kAbl == 0), "B by DMA: rows through registers, final pass, no experiment variants");
-  static_assert(!kDma || (kBf16 && !kL2 && !kSample && !kTiming), "the DMA row path serves a 16-bit row stream in the final pass");
+  static_assert(!kDma || (kBf16 && !kSample && !kTiming), "the DMA row path serves a 16-bit row stream in the final pass");
+  static_assert(!kDma || !kL2 || (!kBfMma && kAbl == 0), "L2 on the DMA row path: the f16 image of f32 rows, no experiment variants");
   // (experiment kernels only, kAbl != 0: a.ablate switches pieces of the pipeline OFF -- results invalid, times tell what bounds a stage:
   //  1 B producers do not store, 2 nor load; 4 row producers do not store, 8 nor load; kAbl 16 / 32: the consumers keep
   //  the B / A fragments they read first)
@@ -1093,7 +1094,7 @@ __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
       // lands on slot l & 7 of row 8 j + l / 8 and therefore fetches the row's piece (l & 7) ^ swizzle(row)).
       // Loads return in order, so the ORDER of the requests decides what a wait costs: B(S+3) is requested BEFORE the rows
       // of stage S+4, and the wait for B(S+1) and the rows of S+1 then leaves rows(S+2), B(S+2), rows(S+3), B(S+3) and
-      // rows(S+4) -- 28 requests -- in flight: nothing is waited for earlier than it is needed.  The B stores are inline
+      // rows(S+4) -- 28 requests (kL2: 30, below) -- in flight: nothing is waited for earlier than it is needed.  The B stores are inline
       // assembly: behind a DMA in flight the compiler would put vmcnt(0) in front of every LDS store it knows about.
       // (kBfMma: the bf16 rows themselves; else the f16 image of an f32 index's rows, FlatFilterArgs::rows16)
       const uint32_t pw = wave - 4;
@@ -1106,7 +1107,16 @@ __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
       const uint32_t ks_n = a.row_stride_f / 16;
       FPos ld{first_tile * row_step, 0, total, row_step}, lb = ld;
       uint32_t slot_i = 0;                                                   // ring slot of the next row request (bytes)
-      struct B8 { u32x4v v[8]; } b0, b1, b2;
+      // kL2: the tile's half norms (hn16) travel WITH the B operands -- one more load per B set, one more LDS store per stage,
+      // so every producer wave keeps one request count and the waits below stay constants.  Wave pw: the words of rows 32 pw ..
+      // 32 pw + 31 of the tile stage S+3 belongs to (both halves of the wave ask for the same 32 words; rows beyond n_rows clamp
+      // as ws_rows_load does), stored with B(S+1) to half (S+1) & 1 of hn_lds -- where the register path's producers put them,
+      // stage by stage, so the consumers' K-step reads them as it always did, behind the barrier that publishes the stage.
+      struct B8 { u32x4v v[8]; uint32_t hn; } b0, b1, b2;
+      b0.hn = b1.hn = b2.hn = 0;
+      constexpr int kInFlight = kL2 ? 30 : 28;                               // requests behind B(S+1) and the rows of S+1 (below)
+      const uint32_t hn_row = 32u * pw + (lane & 31u);
+      const uint32_t hn_lds_at = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)hn_lds) + hn_row * 4u;
 #define VK_WS_DMA_ROWS()                                                                                            \
       {                                                                                                             \
         const __amdgpu_buffer_rsrc_t r_ =                                                                           \
@@ -1125,6 +1135,10 @@ __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
           _Pragma("unroll") for (int kk = 0; kk < 4; ++kk)                                                          \
             B.v[t2 * 4 + kk] = __builtin_amdgcn_raw_buffer_load_b128(r_, (int)(lane * 16 + kk * 1024), 0, 0);       \
         }                                                                                                           \
+        if constexpr (kL2) {                                                                                        \
+          const uint32_t row_ = lb.row0 + hn_row;                                                                   \
+          B.hn = __builtin_amdgcn_raw_buffer_load_b32(ws_rsrc(a.hn16), (int)((row_ < a.n_rows ? row_ : a.n_rows - 1u) * 4u), 0, 0); \
+        }                                                                                                           \
         fpos_advance(lb, stages);                                                                                   \
       }
 #define VK_WS_DMA_BSTORE(B, PAR)                                                                                    \
@@ -1132,15 +1146,26 @@ __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
         const uint32_t at_ = b_lds + (PAR) * (kWsBStage * 16u);                                                     \
         _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_)                                                            \
           asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(at_), "v"(B.v[i_]), "n"(i_ * 1024) : "memory");       \
+        if constexpr (kL2) asm volatile("ds_write_b32 %0, %1" ::"v"(hn_lds_at + (PAR) * (kFTileRows * 4u)), "v"(B.hn) : "memory"); \
       }
+      // (kL2: the requests leave in the order they stand in -- the count above is a count of what was requested BEHIND the rows of
+      //  stage 0, and of stages 1 to 3 in the first iterations; a B or half-norm load moved in front of them would not be among it)
+#define VK_WS_DMA_ORDER() if constexpr (kL2) __builtin_amdgcn_sched_barrier(0);
       VK_WS_DMA_BLOAD(b0)
+      VK_WS_DMA_ORDER()
       VK_WS_DMA_ROWS()
+      VK_WS_DMA_ORDER()
       VK_WS_DMA_BLOAD(b1)
+      VK_WS_DMA_ORDER()
       VK_WS_DMA_ROWS()
+      VK_WS_DMA_ORDER()
       VK_WS_DMA_BLOAD(b2)
+      VK_WS_DMA_ORDER()
       VK_WS_DMA_ROWS()
       VK_WS_DMA_ROWS()
-      asm volatile("s_waitcnt vmcnt(28)" ::: "memory");
+      VK_WS_DMA_ORDER()
+#undef VK_WS_DMA_ORDER
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kInFlight) : "memory");
       VK_WS_DMA_BSTORE(b0, 0u)
       VK_WS_PBARRIER()
       uint32_t bpar = 0;                                                     // S & 1
@@ -1155,7 +1180,7 @@ __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
         if (kAbl == 0 || b_on) VK_WS_DMA_BLOAD(BLOAD)                                                               \
         if (kAbl == 0 || r_on) VK_WS_DMA_ROWS()                                                                     \
         __builtin_amdgcn_sched_barrier(0);                                                                          \
-        asm volatile("s_waitcnt vmcnt(28)" ::: "memory");                                                           \
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kInFlight) : "memory");                                            \
         bpar ^= 1;                                                                                                  \
         if (kAbl == 0 || !(abl & 1u)) VK_WS_DMA_BSTORE(BSTORE, bpar)                                                \
         left_c -= live ? 1u : 0u;                                                                                   \
@@ -1513,22 +1538,23 @@ __global__ __launch_bounds__(kWsThreads, 1) void flat_filter_early_bfmma_dma_m16
   flat_filter_body<true, false, false, false, 0, true, true, false, true>(a);
 }
 // B operands by DMA (rows through registers): the final pass of every row format and space except the bf16 DMA kernel
-// kImage (f32 rows, inner-product space): the pass reads the f16 image of the rows on the DMA row path instead -- under the
-// same symbol, the f32 index's final pass
+// kImage (f32 rows): the pass reads the f16 image of the rows on the DMA row path instead -- under the same symbol, the f32
+// index's final pass.  With kL2 (option flat-l2-image) the producers of that path stage the tile's half norms beside the B
+// operands and the consumers close the tile with the register path's extra K-step: the same operands, the same scores.
 template <bool kBf16, bool kL2, bool kBfMma, bool kImage = false, bool kM16 = false>
 __global__ __launch_bounds__(kWsThreads, 1) void flat_filter_bdma_kernel(FlatFilterArgs a) {
-  static_assert(!kImage || (!kBf16 && !kL2 && !kBfMma), "the f16 image belongs to f32 rows in the inner-product space");
+  static_assert(!kImage || (!kBf16 && !kBfMma), "the f16 image belongs to f32 rows");
   static_assert(!kM16 || (!kBf16 && !kL2 && !kBfMma), "16x16x32: f32 rows in the inner-product space, image and register path alike");
-  if constexpr (kImage) flat_filter_body<true, false, false, false, 0, false, true, false, kM16>(a);
+  if constexpr (kImage) flat_filter_body<true, kL2, false, false, 0, false, true, false, kM16>(a);
   else flat_filter_body<kBf16, kL2, false, false, 0, kBfMma, false, true, kM16>(a);
 }
 // the early pass of a batch that walks the index in two launches (FlatFilterArgs::part_tiles): the final pass's code under its
 // own names
 template <bool kBf16, bool kL2, bool kBfMma, bool kImage = false, bool kM16 = false>
 __global__ __launch_bounds__(kWsThreads, 1) void flat_filter_early_kernel(FlatFilterArgs a) {
-  static_assert(!kImage || (!kBf16 && !kL2 && !kBfMma), "the f16 image belongs to f32 rows in the inner-product space");
+  static_assert(!kImage || (!kBf16 && !kBfMma), "the f16 image belongs to f32 rows");
   static_assert(!kM16 || (!kBf16 && !kL2 && !kBfMma), "16x16x32: f32 rows in the inner-product space, image and register path alike");
-  if constexpr (kImage) flat_filter_body<true, false, false, false, 0, false, true, false, kM16>(a);
+  if constexpr (kImage) flat_filter_body<true, kL2, false, false, 0, false, true, false, kM16>(a);
   else flat_filter_body<kBf16, kL2, false, false, 0, kBfMma, false, true, kM16>(a);
 }
 __global__ __launch_bounds__(kWsThreads, 1) void flat_filter_early_bfmma_dma_kernel(FlatFilterArgs a) {
@@ -1622,9 +1648,12 @@ hipError_t launch_flat_filter(const FlatFilterArgs &a, uint32_t blocks, hipStrea
   }
   // f32 rows with a current f16 image (FlatIndex::scan_filter passes rows16 only then): both passes stream the image
   if (a.rows16 != nullptr && a.mode == 0 && !exp_variant) {
-    if (a.bf16 || a.l2 || a.qbf16) return hipErrorInvalidValue;
+    if (a.bf16 || a.qbf16 || (a.l2 && a.hn16 == nullptr)) return hipErrorInvalidValue;
     fn = a.early ? reinterpret_cast<const void *>(&flat_filter_early_kernel<false, false, false, true>)
                  : reinterpret_cast<const void *>(&flat_filter_bdma_kernel<false, false, false, true>);
+    if (a.l2)   // (the half-norm K-step on the DMA row path)
+      fn = a.early ? reinterpret_cast<const void *>(&flat_filter_early_kernel<false, true, false, true>)
+                   : reinterpret_cast<const void *>(&flat_filter_bdma_kernel<false, true, false, true>);
     lds = flat_filter_dma_lds_bytes();
   }
   // the 16x16x32 consumers (option filter-mfma-shape): the final passes of f32 rows in the inner-product space -- over the image

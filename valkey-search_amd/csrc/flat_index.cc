@@ -1217,7 +1217,7 @@ class FlatIndex final : public Index {
     return Status::Ok();
   }
 
-  // The f16 image of the rows (f32 rows, inner-product space; option flat-f16-image): [alloc_rows + kRowSlack][Dp] f16, the
+  // The f16 image of the rows (f32 rows; inner-product space: option flat-f16-image, L2: option flat-l2-image): [alloc_rows + kRowSlack][Dp] f16, the
   // bytes the filter's row producers make of the f32 rows for every batch, kept instead -- row_stats_kernel writes them for
   // the rows a writer phase touched, and the filter's passes read 2 bytes per element by DMA.  Derived data: not saved,
   // sized like the tile table, re-made whole after a re-allocation (*all).  It is optional: with the option off it is
@@ -1228,12 +1228,18 @@ class FlatIndex final : public Index {
   // the old format), under image_mu_: no batch is between reading the pointer and the format and enqueueing its passes, and the
   // lock is handed back (*hold) and kept until the rewrite has finished on the device (ensure_row_stats waits for it), so no
   // batch ever reads an image that is half one format and half the other.
+  // L2 indexes (option flat-l2-image, off by default): the same image under the same rules, always f16 -- the half norm of a row
+  // is two f16 words (hn16) that close the tile with one more K-step of the f16 instruction; over bf16 operands it would take
+  // three bf16 words and a margin of its own, which nobody has built.
+  bool image_wanted() const {
+    return !store_.bf16() && opt_.get(l2() ? kOptFlatL2Image : kOptFlatF16Image) != 0;
+  }
   void ensure_image(bool wrote, bool *all, std::unique_lock<std::shared_mutex> *hold) {
-    const bool want = !store_.bf16() && !l2() && opt_.get(kOptFlatF16Image) != 0;
+    const bool want = image_wanted();
     const size_t need = want ? (size_t)(store_.alloc_rows() + RowStore::kRowSlack) * store_.stride_f() * 2 : 0;
     if (wrote || image_refused_rows_ != store_.alloc_rows()) image_refused_ = false;
     const uint64_t fopt = opt_.get(kOptFlatImageFormat);   // (2: by size -- the smallest index the bf16 image was measured on)
-    const uint32_t fmt = (fopt == 1 || (fopt == 2 && count_ >= kImageBf16AutoRows)) ? kImageBf16 : kImageF16;
+    const uint32_t fmt = (!l2() && (fopt == 1 || (fopt == 2 && count_ >= kImageBf16AutoRows))) ? kImageBf16 : kImageF16;
     if (want && d_rows16_.p != nullptr && d_rows16_.cap >= need && fmt != image_format_) {
       *hold = std::unique_lock<std::shared_mutex>(image_mu_);
       (void)hipDeviceSynchronize();   // (the passes already enqueued, on whichever stream, still read the old format)
@@ -1346,7 +1352,7 @@ class FlatIndex final : public Index {
     // the f16 image of f32 rows (ensure_image): read by both passes of mode 0 when it is there and wanted (the option is
     // read per batch: an A/B on one index); held shared until the passes are enqueued, against a release in between
     std::shared_lock<std::shared_mutex> image_lk(image_mu_);
-    f.rows16 = (!store_.bf16() && !l2() && !filter_experiment && !filter_dump_active() && opt_.get(kOptFlatF16Image) != 0) ? d_rows16_.p : nullptr;
+    f.rows16 = (image_wanted() && !filter_experiment && !filter_dump_active()) ? d_rows16_.p : nullptr;
     last_filter_image_bytes_.store(f.rows16 ? (uint64_t)store_.alloc_rows() * dp * 2 : 0, std::memory_order_relaxed);
     // a bf16 image (option flat-image-format = 1; the format the image HOLDS decides, under the lock): the image stands in for the
     // rows of a bf16 index in every filter pass, the sample included -- bf16 fragments, the bf16 matrix-core instruction, rows by

@@ -169,9 +169,9 @@ struct FlatGemmArgs {
 // K4h (flat_filter.hip): candidate stage of the batched FLAT search on the f16 matrix cores
 struct FlatFilterArgs {
   const void *rows;           // f32 or (bf16 = 1) bf16 rows, row_stride_f elements apart
-  // f32 rows, inner-product space: the f16 image of the rows, [row][row_stride_f] (row_stats_kernel keeps it current), or
-  // nullptr = none.  With it the passes of mode 0 read 2 bytes per element by DMA instead of 4 through registers; the
-  // sample pass and the re-rank keep reading `rows`.
+  // f32 rows: the f16 image of the rows, [row][row_stride_f] (row_stats_kernel keeps it current), or nullptr = none.  With it
+  // the passes of mode 0 read 2 bytes per element by DMA instead of 4 through registers (l2: and the half norms from hn16 in
+  // the producers of that path); the sample pass and the re-rank keep reading `rows`.
   const void *rows16;
   uint32_t bf16;
   uint32_t l2;                // squared Euclidean distance instead of 1 - dot

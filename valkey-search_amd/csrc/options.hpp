@@ -55,6 +55,8 @@ enum OptId : uint32_t {
   kOptPrefilterLabelMapUpkeep, kOptPrefilterLabelMapDeltaMax,
   // ---- FLAT k > 1024 in one row pass: the hand-back ordered on the device ------------------------------------------------------
   kOptFlatLargeKDeviceSort,
+  // ---- FLAT, f32 rows under L2: the filter's early and main pass over the f16 image of the rows ---------------------------------
+  kOptFlatL2Image,
   kOptCount
 };
 
@@ -153,6 +155,11 @@ inline const OptDesc &opt_desc(uint32_t id) {
       // read per call, nothing changes while flat-large-k is 0.  Ships off: it goes on by default only once
       // scripts/flat_large_k_probe.py shows no point below the host-sort median
       {"flat-large-k-device-sort", nullptr, 0, 0, 1},
+      // f32 rows under L2: the filter's early and main pass read a resident f16 image of the rows by DMA (+50 % of the row table)
+      // and take the half norms from hn16 in the producers of that path, instead of 4 bytes per element through registers; always
+      // f16, whatever flat-image-format says.  Read per batch, 0 releases the image.  Ships off: it goes on by default only once
+      // scripts/flat_l2_image_probe.py shows no point below the option-off median
+      {"flat-l2-image", nullptr, 0, 0, 1},
   };
   return t[id];
 }
