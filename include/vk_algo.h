@@ -165,6 +165,13 @@ class Algo {
     Check(vk_index_large_k_sort_stats(ix_, &s));
     return s;
   }
+  // shared-list pre-filter distances on the matrix cores (vk_index_prefilter_mfma_stats; option prefilter-shared-mfma = 1)
+  vk_prefilter_mfma_stats prefilterMfmaStats() const {
+    vk_prefilter_mfma_stats s;
+    s.struct_size = sizeof(s);
+    Check(vk_index_prefilter_mfma_stats(ix_, &s));
+    return s;
+  }
   // the device label map across write phases (vk_index_label_map_stats; option prefilter-label-map-upkeep = 1: touched labels
   // applied on the device instead of a rebuild per phase)
   vk_label_map_stats labelMapStats() const {

@@ -520,6 +520,21 @@ typedef struct vk_flat_large_k_sort_stats {
   uint64_t finish_ns;           /* ... the host's loop over the hand-back (the sort, or the copy), by the host's clock */
 } vk_flat_large_k_sort_stats;
 int vk_index_large_k_sort_stats(vk_index *ix, vk_flat_large_k_sort_stats *out);
+/* K8m, in a struct of its own (vk_prefilter_stats_v2 and vk_filter_exact_stats keep their sizes): set struct_size =
+ * sizeof(vk_prefilter_mfma_stats) before the call.  With option prefilter-shared-mfma = 1 a pre-filter batch over a SHARED list
+ * (vk_index_search_labels_batch with list_begin == NULL, every run of vk_index_search_filter_exact_batch, a collected lane of
+ * vk_index_search_labels_submit whose members brought the same list) takes its distances from the matrix cores when the metric
+ * is IP or COSINE, the chunk holds at least 5 queries and the row stride is at most 1664 floats; the bits are those of the
+ * per-query kernel, so the answers do not change.  With 0 (the default) every counter stays 0.  A sharded index answers the
+ * sums of its shards. */
+typedef struct vk_prefilter_mfma_stats {
+  uint64_t struct_size;
+  uint64_t launches;   /* shared-list distance launches that ran on the matrix cores */
+  uint64_t queries;    /* ... and their queries */
+  uint64_t entries;    /* ... and their list entries (once per launch, not per query) */
+  uint64_t declined;   /* shared-list launches that stayed on K8b while the option was 1 (metric, stride, fewer than 5 queries) */
+} vk_prefilter_mfma_stats;
+int vk_index_prefilter_mfma_stats(vk_index *ix, vk_prefilter_mfma_stats *out);
 /* The device label map across write phases, in a struct of its own (vk_prefilter_stats_v2 keeps its size): set struct_size =
  * sizeof(vk_label_map_stats) before the call.  The map (label -> row slot / internal id, used by vk_index_search_labels_batch
  * with prefilter-device-resolve = 1 and always by vk_index_search_filter_exact_batch) is tagged with the publication it was
@@ -580,7 +595,9 @@ int vk_index_search_batch_filter_handles(vk_index *ix, const void *queries, uint
  *   lookup per key; same answers, and a map that finds no room -- on the device, or within prefilter-label-map-bytes, 1 GiB --
  *   leaves the batch on the host's lookups), prefilter-label-map-upkeep (0 / 1, read per batch, ships 0: behind a write phase
  *   the labels it touched are applied to that map on the device instead of the rebuild; vk_label_map_stats),
- *   prefilter-label-map-delta-max (1 .. 1 << 24, default 65 536: a phase that touched more labels has the map rebuilt), ...
+ *   prefilter-label-map-delta-max (1 .. 1 << 24, default 65 536: a phase that touched more labels has the map rebuilt),
+ *   prefilter-shared-mfma (0 / 1, read per batch, ships 0: a pre-filter batch over a shared list takes its distances from the
+ *   matrix cores -- IP / COSINE, at least 5 queries, row strides up to 1664 floats; same answers; vk_prefilter_mfma_stats), ...
  * A sharded index applies an option to itself and to every shard.  Unknown name or value out of range: VK_ERR_INVALID.
  * Options take effect for searches that START after the call; no search path reads the environment. */
 int vk_index_set_option(vk_index *ix, const char *name, uint64_t value);

@@ -533,6 +533,7 @@ class HnswIndex final : public Index {
     // labels the lookup below accepts.
     bool on_device = false;
     LabelMapTable map;
+    want_mfma(lease.ctx);
     if (opt_.get(kOptPrefilterDeviceResolve) != 0 && label_map_ready(lease.ctx->stream, &map)) {
       uint64_t resolved = 0;
       VK_TRY(prefilter_device_stage_keys(lease.ctx, map, store_.d_rows(), params_.dim, store_.stride_f(), l2(), store_.bf16(), queries, nq, k,
@@ -547,6 +548,7 @@ class HnswIndex final : public Index {
       }, &r);
       VK_TRY(prefilter_device_stage(lease.ctx, store_.d_rows(), params_.dim, store_.stride_f(), l2(), store_.bf16(), queries, k, r, out));
     }
+    fold_mfma(lease.ctx);
     uint64_t cands = 0;
     for (uint64_t q = 0; q < nq; ++q)
       if (!out->fallback[q]) cands += out->begin[q + 1] - out->begin[q];
@@ -570,8 +572,10 @@ class HnswIndex final : public Index {
     LabelMapTable map;
     const bool have = label_map_ready(lease.ctx->stream, &map);
     uint64_t expanded = 0, known = 0;
+    want_mfma(lease.ctx);
     VK_TRY(prefilter_handle_stage(lease.ctx, have ? &map : nullptr, bits, f.nbits(), f.allowed(), store_.d_rows(), params_.dim, store_.stride_f(),
                                   l2(), store_.bf16(), queries, nq, k, out, &expanded, &known));
+    fold_mfma(lease.ctx);
     count_handle_stage(*out, expanded, known);
     return Status::Ok();
   }

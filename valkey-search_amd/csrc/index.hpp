@@ -110,6 +110,10 @@ struct SearchCtx {
   // replaced by the context's next user
   std::vector<std::shared_ptr<const void>> keep_alive;
   PinBuf h_q, h_out_d, h_out_l, h_out_n, h_tmp, h_idx, h_cancel, h_lk;
+  // K8m (option prefilter-shared-mfma): the index writes its wish before it calls a pre-filter driver, the driver adds what its
+  // shared-list launches did, the index folds that into its counters afterwards (Index::fold_mfma)
+  bool pf_mfma_want = false;
+  PrefilterMfmaCount pf_mfma;
   // per-member cancellation (SearchRequest::member_cancel): the words the kernel polls follow the batch word in h_cancel
   static constexpr size_t kMemberCancelOffset = 16;   // in u32 words
   Status wait(const volatile int *caller_flag, const volatile uint32_t *member_cancel, uint64_t nq);
@@ -267,6 +271,16 @@ class Index {
     out->struct_size = sizeof(*out);
     return Status::Ok();
   }
+  // vk_index_prefilter_mfma_stats (a sharded index sums its shards)
+  virtual Status prefilter_mfma_stats(vk_prefilter_mfma_stats *out) {
+    memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    out->launches = mf_.launches.load(std::memory_order_relaxed);
+    out->queries = mf_.queries.load(std::memory_order_relaxed);
+    out->entries = mf_.entries.load(std::memory_order_relaxed);
+    out->declined = mf_.declined.load(std::memory_order_relaxed);
+    return Status::Ok();
+  }
   // vk_index_label_map_stats (a sharded index sums its shards) / vk_index_label_map_read (a plain index only)
   virtual Status label_map_stats(vk_label_map_stats *out) {
     memset(out, 0, sizeof(*out));
@@ -346,6 +360,23 @@ class Index {
       out->downloaded_runs = downloaded_runs.load(std::memory_order_relaxed);
     }
   } hx_;
+  // ... and of K8m (vk_prefilter_mfma_stats).  A leaf brackets its driver call: want_mfma before, fold_mfma behind.  The option
+  // is read per batch; it goes on by default only once scripts/prefilter_mfma_probe.py shows no point below the option-off median
+  struct MfmaCounters {
+    std::atomic<uint64_t> launches{0}, queries{0}, entries{0}, declined{0};
+  } mf_;
+  void want_mfma(SearchCtx *ctx) {
+    ctx->pf_mfma_want = opt_.get(kOptPrefilterSharedMfma) != 0;
+    ctx->pf_mfma = PrefilterMfmaCount{};
+  }
+  void fold_mfma(SearchCtx *ctx) {
+    mf_.launches.fetch_add(ctx->pf_mfma.launches, std::memory_order_relaxed);
+    mf_.queries.fetch_add(ctx->pf_mfma.queries, std::memory_order_relaxed);
+    mf_.entries.fetch_add(ctx->pf_mfma.entries, std::memory_order_relaxed);
+    mf_.declined.fetch_add(ctx->pf_mfma.declined, std::memory_order_relaxed);
+    ctx->pf_mfma_want = false;
+    ctx->pf_mfma = PrefilterMfmaCount{};
+  }
   // what a leaf's handle_candidates adds after its device stage
   void count_handle_stage(const HandleCands &c, uint64_t expanded, uint64_t known) {
     uint64_t cands = 0;

@@ -499,6 +499,9 @@ struct PrefilterDistArgs {
   float *out;
   uint32_t row_stride_f, q_stride_f, chunks;
   uint32_t nq, shared_len, n_tiles;
+  // 1: the caller wishes K8m (prefilter_mfma_kernel: the same bits from the matrix cores, a shared list in the inner-product
+  // space only); the launcher takes it when prefilter_takes_mfma (prefilter_host.hpp) agrees and runs K8b otherwise
+  uint32_t mfma;
 };
 // K8c: per query, over its segment of `dist` (laid out as K8b's out): count[q] = entries at or below T = the k-th
 // smallest distance (the maximum when the segment is shorter than k), cand[q][0 .. min(count, cap)) = the first of them in

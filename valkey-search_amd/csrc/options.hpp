@@ -57,6 +57,8 @@ enum OptId : uint32_t {
   kOptFlatLargeKDeviceSort,
   // ---- FLAT, f32 rows under L2: the filter's early and main pass over the f16 image of the rows ---------------------------------
   kOptFlatL2Image,
+  // ---- batched pre-filter search: a shared list's distances on the matrix cores (K8m) ------------------------------------------
+  kOptPrefilterSharedMfma,
   kOptCount
 };
 
@@ -160,6 +162,11 @@ inline const OptDesc &opt_desc(uint32_t id) {
       // f16, whatever flat-image-format says.  Read per batch, 0 releases the image.  Ships off: it goes on by default only once
       // scripts/flat_l2_image_probe.py shows no point below the option-off median
       {"flat-l2-image", nullptr, 0, 0, 1},
+      // pre-filter batches over a SHARED list, IP / COSINE, at least 5 queries in the chunk: the distances come from K8m
+      // (prefilter_mfma_kernel: v_mfma_f32_32x32x2_f32 over gathered rows, the bits of K8b) instead of one K8b block per (query,
+      // tile); L2, per-query lists, shorter chunks and strides K8m cannot hold run K8b as before.  Read per batch.  Ships off: it
+      // goes on by default only once scripts/prefilter_mfma_probe.py shows no point below the option-off median
+      {"prefilter-shared-mfma", nullptr, 0, 0, 1},
   };
   return t[id];
 }

@@ -94,6 +94,7 @@ Status prefilter_device_stage(SearchCtx *ctx, const void *d_rows, uint32_t dim, 
     da.nq = (uint32_t)cq;
     da.shared_len = r.shared ? (uint32_t)n_slots : 0;
     da.n_tiles = r.shared ? 0 : tile[cq];
+    da.mfma = prefilter_mfma_decide(ctx->pf_mfma_want, &ctx->pf_mfma, r.shared, l2, stride_f, cq, n_slots);
     VK_HIP_TRY(launch_prefilter_distance(da, l2, bf16, ctx->stream));
     PrefilterSelectArgs sa{};
     sa.dist = da.out;

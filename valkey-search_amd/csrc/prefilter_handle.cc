@@ -108,6 +108,7 @@ Status prefilter_handle_stage(SearchCtx *ctx, const LabelMapTable *map, const ui
     da.chunks = stride_f / 16;
     da.nq = (uint32_t)cq;
     da.shared_len = (uint32_t)entries;
+    da.mfma = prefilter_mfma_decide(ctx->pf_mfma_want, &ctx->pf_mfma, true, l2, stride_f, cq, entries);
     VK_HIP_TRY(launch_prefilter_distance(da, l2, bf16, ctx->stream));
     PrefilterSelectArgs sa{};
     sa.dist = da.out;

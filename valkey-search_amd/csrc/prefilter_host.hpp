@@ -36,6 +36,40 @@ constexpr uint64_t kPrefilterChunkEntries = 1ull << 24;   // x 4 B
 constexpr uint64_t kPrefilterChunkBytes = 64ull << 20;
 constexpr uint32_t kPrefilterCountNaN = 0xFFFFFFFFu;      // the select kernel's count word of a segment that holds a NaN
 
+// ---- K8m: a shared list's distances on the matrix cores (option prefilter-shared-mfma) ----------------------------------
+// One decision, asked by the three drivers (prefilter_batch.cc, prefilter_resolve.cc, prefilter_handle.cc: what they count)
+// and by launch_prefilter_distance (prefilter_select.hip: what runs), so the two cannot disagree.
+constexpr uint64_t kPrefilterMfmaMinQueries = 5;   // FlatIndex::kGemmMinQueries: below it the per-query kernel wins (K3 against K4, flat_index.cc)
+constexpr uint64_t kPrefilterMfmaRingBytes = 4 * 3 * 32 * 36 * 4;   // four waves x three stages of [32 rows][36 dwords]
+// queries per block for rows of stride_f floats: 32 (the matrix tile's width) while the resident query tile, rows of
+// stride_f + 4 floats, fits the 160 KB of a CU beside the staging rings, then 24 or 16 (K4's rule, flat_gemm_tile_q); 0 = a
+// stride the kernel cannot hold -- not whole 2-chunk stage pairs, or too long for 16 queries
+inline uint32_t prefilter_mfma_tile_q(uint64_t stride_f) {
+  if (stride_f == 0 || stride_f % 64 != 0) return 0;
+  for (uint32_t tq : {32u, 24u, 16u})
+    if (tq * (stride_f + 4) * 4 + kPrefilterMfmaRingBytes <= 160 * 1024) return tq;
+  return 0;
+}
+inline bool prefilter_takes_mfma(bool wanted, bool shared, bool l2, uint64_t stride_f, uint64_t nq) {
+  return wanted && shared && !l2 && nq >= kPrefilterMfmaMinQueries && prefilter_mfma_tile_q(stride_f) != 0;
+}
+// what a driver did with its shared-list launches (vk_prefilter_mfma_stats); the index folds it into its atomics
+struct PrefilterMfmaCount {
+  uint64_t launches = 0, queries = 0, entries = 0, declined = 0;
+};
+// the decision for one launch, counted: returns PrefilterDistArgs::mfma
+inline uint32_t prefilter_mfma_decide(bool wanted, PrefilterMfmaCount *c, bool shared, bool l2, uint64_t stride_f, uint64_t nq, uint64_t entries) {
+  if (!wanted || !shared) return 0;
+  if (!prefilter_takes_mfma(true, true, l2, stride_f, nq)) {
+    ++c->declined;
+    return 0;
+  }
+  ++c->launches;
+  c->queries += nq;
+  c->entries += entries;
+  return 1;
+}
+
 // vector_base.cc:509-530: fill to k, then a key replaces the heap top only when its distance is strictly smaller (ties
 // keep what is already there); labels[i] == UINT64_MAX = unknown key, skipped.  Output ascending by (distance, label).
 inline void prefilter_heap_rule(const float *dist, const uint64_t *labels, uint64_t n, uint64_t k, float *out_dist,

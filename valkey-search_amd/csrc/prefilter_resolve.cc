@@ -313,6 +313,7 @@ Status prefilter_device_stage_keys(SearchCtx *ctx, const LabelMapTable &map, con
     da.nq = (uint32_t)cq;
     da.shared_len = shared ? (uint32_t)entries : 0;
     da.n_tiles = shared ? 0 : r.h_tile[cq];
+    da.mfma = prefilter_mfma_decide(ctx->pf_mfma_want, &ctx->pf_mfma, shared, l2, stride_f, cq, entries);
     VK_HIP_TRY(launch_prefilter_distance(da, l2, bf16, ctx->stream));
     PrefilterSelectArgs sa{};
     sa.dist = da.out;

@@ -33,6 +33,8 @@
 #include "kernels.hpp"
 #include "prefilter_host.hpp"
 
+#include <algorithm>
+
 namespace vk {
 
 namespace {
@@ -85,6 +87,281 @@ __global__ __launch_bounds__(256) void prefilter_distance_kernel(PrefilterDistAr
   const uint32_t row = a.idx[seg_lo + (valid ? i : seg_len - 1)];
   const float dist = quad_row_distance<kL2, kBf16>(row_base<kBf16>(a.rows, row, a.row_stride_f), qs, chunks, j);
   if (valid && j == 0) a.out[out_lo + i] = dist;
+}
+
+// ---- K8m: the distances of a shared list on the matrix cores ---------------------------------------------------------------
+// K4's arithmetic (flat_gemm.hip) on gathered rows with a dense output.  The f32-input MFMA is a k-ordered fmaf chain, so one
+// accumulator tile per lane class l, fed (chunk c, element l), (chunk c + 1, element l), ... in order, is chain l of
+// quad_row_distance for 32 x 32 (query, entry) pairs at once; the 16 tiles are combined with quad_reduce16's tree.
+//   block tile  = 128 list entries x tq queries (prefilter_mfma_tile_q); wave w owns entries [32w, 32w + 32) of the tile
+//   operands    : A = queries, B = rows (a * b commutes: the bits are K4's), so a lane holds ONE entry for 16 queries and
+//                 every output register is stored as 32 consecutive floats of one query's row of `out`
+//   Q tile      : resident in LDS for the whole block, [tq][stride + 4] f32 (the pad keeps ds_read_b128 conflict free)
+//   rows        : each wave gathers ITS 32 rows HBM -> registers -> its private LDS ring (3 stages of [32 rows][2 chunks], row
+//                 stride 36 dwords) -> MFMA operands; no block barrier behind the Q tile's.  A lane reads its row slots once
+//                 per tile and keeps the row bases in registers; the slots of the tile after the loader's are fetched a whole
+//                 tile ahead, so the gather's dependent load never stands in front of a stage
+//   grid        : nrp x nqt blocks, nrp (a multiple of 8) from the CU count; a block loads its query tile once and walks a
+//                 contiguous range of row tiles; the nqt blocks of a range sit on one XCD, adjacent in dispatch order
+// Entries past shared_len re-read the last valid one and are not stored; no row but idx[]'s is touched.
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+constexpr uint32_t kMfmaTile = 128;
+constexpr uint32_t kMfmaXStride = 36;                     // dwords per staged row: 2 chunks + 4 pad
+constexpr uint32_t kMfmaBufFloats = 32 * kMfmaXStride;    // one stage of one wave
+constexpr uint32_t kMfmaBufs = 3;
+static_assert(kPrefilterMfmaRingBytes == 4 * kMfmaBufs * kMfmaBufFloats * 4, "prefilter_mfma_tile_q budgets this ring");
+
+// register-resident sets are plain structs handled BY VALUE (K4's note: arrays by reference end up in scratch)
+struct MfmaStg { float4 v0, v1, v2, v3; };
+struct MfmaFrag { float4 q0, q1, q2, q3, x0, x1, x2, x3; };
+struct MfmaSlots { uint32_t s0, s1, s2, s3; };
+struct MfmaBases { const char *b0, *b1, *b2, *b3; };
+
+// which rows of its wave's 32 a lane stages.  f32: a stage of a row is 8 pieces of 16 B, lane -> row lane / 8 (+ 8, 16, 24),
+// piece lane % 8.  bf16: 4 pieces, lane -> a row of the first 16 (+ 16), piece lane % 4; the 16 lanes of a store pass take rows
+// {2G, 2G + 1, 2G + 8, 2G + 9} so that their stores land in 16 different bank groups (K4's bf16_lane_row)
+template <bool kBf16>
+__device__ __forceinline__ uint32_t mfma_lane_row(uint32_t lane) {
+  if constexpr (kBf16) {
+    const uint32_t G = lane >> 4, rr = (lane >> 2) & 3;
+    return 2 * G + (rr & 1) + 8 * (rr >> 1);
+  } else {
+    return lane >> 3;
+  }
+}
+// the row slots of this lane's rows in tile `tile` (any tile: entries past the list re-read its last one)
+template <bool kBf16>
+__device__ __forceinline__ MfmaSlots mfma_tile_slots(const PrefilterDistArgs &a, uint32_t tile, uint32_t wave, uint32_t lane) {
+  const uint32_t last = a.shared_len - 1;
+  const uint32_t e = tile * kMfmaTile + wave * 32 + mfma_lane_row<kBf16>(lane);
+  constexpr uint32_t step = kBf16 ? 16 : 8;
+  MfmaSlots s;
+  s.s0 = a.idx[e < last ? e : last];
+  s.s1 = a.idx[e + step < last ? e + step : last];
+  if constexpr (kBf16) {
+    s.s2 = s.s0;
+    s.s3 = s.s0;
+  } else {
+    s.s2 = a.idx[e + 2 * step < last ? e + 2 * step : last];
+    s.s3 = a.idx[e + 3 * step < last ? e + 3 * step : last];
+  }
+  return s;
+}
+template <bool kBf16>
+__device__ __forceinline__ MfmaBases mfma_bases(const PrefilterDistArgs &a, const MfmaSlots s, uint32_t lane) {
+  const uint32_t piece = (kBf16 ? lane & 3 : lane & 7) * 16;
+  MfmaBases b;
+  b.b0 = row_base<kBf16>(a.rows, s.s0, a.row_stride_f) + piece;
+  b.b1 = row_base<kBf16>(a.rows, s.s1, a.row_stride_f) + piece;
+  b.b2 = row_base<kBf16>(a.rows, s.s2, a.row_stride_f) + piece;
+  b.b3 = row_base<kBf16>(a.rows, s.s3, a.row_stride_f) + piece;
+  return b;
+}
+// global -> registers, one stage (2 chunks) of the wave's 32 rows: one 64-bit add per 16-byte load
+template <bool kBf16>
+__device__ __forceinline__ MfmaStg mfma_stage_load(const MfmaBases b, uint32_t st) {
+  const uint32_t off = st * (kBf16 ? 64u : 128u);
+  MfmaStg s;
+  s.v0 = *reinterpret_cast<const float4 *>(b.b0 + off);
+  s.v1 = *reinterpret_cast<const float4 *>(b.b1 + off);
+  if constexpr (kBf16) {
+    s.v2 = s.v0;
+    s.v3 = s.v0;
+  } else {
+    s.v2 = *reinterpret_cast<const float4 *>(b.b2 + off);
+    s.v3 = *reinterpret_cast<const float4 *>(b.b3 + off);
+  }
+  return s;
+}
+// eight bf16 (one 16-byte piece) -> two float4: a 16-bit shift, exact
+__device__ __forceinline__ void mfma_widen8(const float4 raw, float4 &lo, float4 &hi) {
+  const uint32_t w0 = __float_as_uint(raw.x), w1 = __float_as_uint(raw.y), w2 = __float_as_uint(raw.z), w3 = __float_as_uint(raw.w);
+  lo = float4{__uint_as_float(w0 << 16), __uint_as_float(w0 & 0xffff0000u), __uint_as_float(w1 << 16), __uint_as_float(w1 & 0xffff0000u)};
+  hi = float4{__uint_as_float(w2 << 16), __uint_as_float(w2 & 0xffff0000u), __uint_as_float(w3 << 16), __uint_as_float(w3 & 0xffff0000u)};
+}
+template <bool kBf16>
+__device__ __forceinline__ void mfma_stage_store(float *buf, uint32_t lane, const MfmaStg s) {
+  if constexpr (kBf16) {
+    // the raw pieces are made opaque HERE, one stage after their load was issued: otherwise the compiler widens a piece right
+    // behind its load and every stage waits for the round trip it has just started (K4)
+    float4 r0 = s.v0, r1 = s.v1;
+    asm volatile("" : "+v"(r0.x), "+v"(r0.y), "+v"(r0.z), "+v"(r0.w), "+v"(r1.x), "+v"(r1.y), "+v"(r1.z), "+v"(r1.w));
+    float4 a0, a1, b0, b1;
+    mfma_widen8(r0, a0, a1);
+    mfma_widen8(r1, b0, b1);
+    float *p0 = buf + mfma_lane_row<true>(lane) * kMfmaXStride + (lane & 3) * 8;
+    float *p1 = p0 + 16 * kMfmaXStride;
+    *reinterpret_cast<float4 *>(p0) = a0;
+    *reinterpret_cast<float4 *>(p0 + 4) = a1;
+    *reinterpret_cast<float4 *>(p1) = b0;
+    *reinterpret_cast<float4 *>(p1 + 4) = b1;
+  } else {
+    float *p = buf + (lane >> 3) * kMfmaXStride + (lane & 7) * 4;
+    *reinterpret_cast<float4 *>(p) = s.v0;
+    *reinterpret_cast<float4 *>(p + 8 * kMfmaXStride) = s.v1;
+    *reinterpret_cast<float4 *>(p + 16 * kMfmaXStride) = s.v2;
+    *reinterpret_cast<float4 *>(p + 24 * kMfmaXStride) = s.v3;
+  }
+}
+// LDS -> registers: this lane's query (A) and row (B) operands of one stage: lane = (query or entry lane & 31, chunk lane >> 5)
+__device__ __forceinline__ MfmaFrag mfma_frag_load(const float *xb, const float *q_row, uint32_t st, uint32_t kk) {
+  const float *qb = q_row + (st * 2 + kk) * 16;
+  MfmaFrag f;
+  f.x0 = *reinterpret_cast<const float4 *>(xb);
+  f.x1 = *reinterpret_cast<const float4 *>(xb + 4);
+  f.x2 = *reinterpret_cast<const float4 *>(xb + 8);
+  f.x3 = *reinterpret_cast<const float4 *>(xb + 12);
+  f.q0 = *reinterpret_cast<const float4 *>(qb);
+  f.q1 = *reinterpret_cast<const float4 *>(qb + 4);
+  f.q2 = *reinterpret_cast<const float4 *>(qb + 8);
+  f.q3 = *reinterpret_cast<const float4 *>(qb + 12);
+  return f;
+}
+
+#define VK_PF_MFMA4(P, QV, XV)                                                                                \
+  acc[4 * P + 0] = __builtin_amdgcn_mfma_f32_32x32x2f32(QV.x, XV.x, kZeroC ? zero : acc[4 * P + 0], 0, 0, 0); \
+  acc[4 * P + 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(QV.y, XV.y, kZeroC ? zero : acc[4 * P + 1], 0, 0, 0); \
+  acc[4 * P + 2] = __builtin_amdgcn_mfma_f32_32x32x2f32(QV.z, XV.z, kZeroC ? zero : acc[4 * P + 2], 0, 0, 0); \
+  acc[4 * P + 3] = __builtin_amdgcn_mfma_f32_32x32x2f32(QV.w, XV.w, kZeroC ? zero : acc[4 * P + 3], 0, 0, 0);
+template <bool kZeroC>
+__device__ __forceinline__ void mfma_stage_mul(f32x16 (&acc)[16], const MfmaFrag f) {
+  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  VK_PF_MFMA4(0, f.q0, f.x0)
+  VK_PF_MFMA4(1, f.q1, f.x1)
+  VK_PF_MFMA4(2, f.q2, f.x2)
+  VK_PF_MFMA4(3, f.q3, f.x3)
+}
+#undef VK_PF_MFMA4
+
+// nrp row partitions (a multiple of 8) x nqt query tiles of tq; a.row_stride_f a multiple of 64, a.chunks = a.row_stride_f / 16
+template <bool kBf16>
+__global__ __launch_bounds__(256, 1) void prefilter_mfma_kernel(PrefilterDistArgs a, uint32_t nrp, uint32_t nqt, uint32_t tq) {
+  extern __shared__ float4 mfma_lds[];
+  float *lds = reinterpret_cast<float *>(mfma_lds);
+  const uint32_t tid = threadIdx.x;
+  const uint32_t lane = tid & 63;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: keep it in a scalar register
+  const uint32_t li = lane & 31;   // query (A) / entry (B) index inside the 32-wide MFMA tile
+  const uint32_t kk = lane >> 5;   // which of the two chunks of the stage this lane feeds
+  const uint32_t width = a.row_stride_f;
+  const uint32_t stages = width / 32;   // even: the ping-pong register sets keep their parity from tile to tile
+  const uint32_t qstride = width + 4;
+  // blocks b and b + 8 share an XCD: the nqt blocks that walk one row range are neighbours there (K8b's and K4's dealing)
+  const uint32_t xcd = blockIdx.x & 7u, seq = blockIdx.x >> 3;
+  const uint32_t rp = (seq / nqt) * 8u + xcd;
+  const uint32_t q0 = (seq % nqt) * tq;
+  const uint32_t n_tiles = (a.shared_len + kMfmaTile - 1) / kMfmaTile;
+  const uint32_t t_base = n_tiles / nrp, t_rem = n_tiles % nrp;
+  const uint32_t first_tile = rp * t_base + (rp < t_rem ? rp : t_rem);
+  const uint32_t my_tiles = t_base + (rp < t_rem ? 1u : 0u);
+  if (my_tiles == 0) return;   // (block-uniform) more partitions than tiles
+
+  float *lds_q = lds;   // [tq][qstride], read-only behind the barrier
+  float *lds_x = lds + (size_t)tq * qstride + (size_t)wave * kMfmaBufs * kMfmaBufFloats;
+  // ---- Q tile -> LDS (queries past nq replicate the last one; their results are discarded)
+  for (uint32_t i = tid; i < tq * (width / 4); i += 256) {
+    const uint32_t q = i / (width / 4), c4 = i % (width / 4);
+    const uint32_t gq = q0 + q < a.nq ? q0 + q : a.nq - 1;
+    *reinterpret_cast<float4 *>(lds_q + (size_t)q * qstride + c4 * 4) = reinterpret_cast<const float4 *>(a.queries + (size_t)gq * a.q_stride_f)[c4];
+  }
+
+  // ---- the loader's place in this block's flattened (tile, stage) stream.  `rb` = its tile's row bases, `next` = the slots of
+  // the tile behind it, requested when the loader entered its tile and looked at only when it leaves it.  The loader never moves
+  // past the last stage of the stream: the prefetches issued behind the end re-read that stage and are not used.
+  uint32_t ld_tile = first_tile, ld_st = 0, ld_left = my_tiles * stages;   // (< 2^32: at most 2^25 tiles of at most 52 stages)
+  MfmaBases rb = mfma_bases<kBf16>(a, mfma_tile_slots<kBf16>(a, ld_tile, wave, lane), lane);
+  MfmaSlots next = mfma_tile_slots<kBf16>(a, ld_tile + 1, wave, lane);
+#define VK_PF_ADVANCE()                                            \
+  if (ld_left > 1) { /* (wave-uniform, between two stages) */      \
+    --ld_left;                                                     \
+    if (++ld_st == stages) {                                       \
+      ld_st = 0;                                                   \
+      ++ld_tile;                                                   \
+      rb = mfma_bases<kBf16>(a, next, lane);                       \
+      next = mfma_tile_slots<kBf16>(a, ld_tile + 1, wave, lane);   \
+    }                                                              \
+  }
+  // Software pipeline over the stream, iteration i = stage i (K4's): the global loads of stage i + 3 are issued at the top of
+  // i, written to LDS at the bottom of i + 1, read LDS -> registers during i + 2, multiplied during i + 3.  Stage s lives in
+  // ring buffer s % 3.  Unrolled by two with ping-pong register sets.
+  MfmaStg stg_a, stg_b;
+  stg_a = mfma_stage_load<kBf16>(rb, ld_st);
+  mfma_stage_store<kBf16>(lds_x, lane, stg_a);
+  VK_PF_ADVANCE()
+  stg_a = mfma_stage_load<kBf16>(rb, ld_st);
+  mfma_stage_store<kBf16>(lds_x + kMfmaBufFloats, lane, stg_a);
+  VK_PF_ADVANCE()
+  stg_a = mfma_stage_load<kBf16>(rb, ld_st);
+  stg_b = stg_a;
+  VK_PF_ADVANCE()
+  __syncthreads();   // the shared Q tile is in place
+
+  const uint32_t x_off = li * kMfmaXStride + kk * 16;
+  const float *q_row = lds_q + (size_t)(li < tq ? li : tq - 1) * qstride;
+  MfmaFrag f0 = mfma_frag_load(lds_x + x_off, q_row, 0, kk), f1 = f0;
+  uint32_t rbuf = 1;   // buffer of stage done + 1
+  uint32_t wbuf = 2;   // buffer of stage done + 2
+
+  // one iteration: F = fragments of stage ST, NF receives the next stage's, SNEW the loads of stage done + 3, SOLD (the loads
+  // of stage done + 2) goes to LDS; the memory operations are pinned between the 16 MFMAs as in K4:
+  //   M V M V M V M V | R R R R | M M M M | R R | M W M W M W M W | R R | M M M M
+#define VK_PF_STAGE(ZERO, ST, F, NF, SNEW, SOLD)                                                  \
+  {                                                                                               \
+    const uint32_t nst = (ST) + 1 == stages ? 0u : (ST) + 1;                                      \
+    SNEW = mfma_stage_load<kBf16>(rb, ld_st);                                                     \
+    mfma_stage_mul<ZERO>(acc, F);                                                                 \
+    NF = mfma_frag_load(lds_x + rbuf * kMfmaBufFloats + x_off, q_row, nst, kk);                   \
+    mfma_stage_store<kBf16>(lds_x + wbuf * kMfmaBufFloats, lane, SOLD);                           \
+    _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                               \
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                          \
+      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                                          \
+    }                                                                                             \
+    __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);                                            \
+    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                                            \
+    __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);                                            \
+    _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                               \
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                          \
+      if constexpr (kBf16) __builtin_amdgcn_sched_group_barrier(0x002, 4, 0); /* widen a float4 */ \
+      __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                                          \
+    }                                                                                             \
+    __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);                                            \
+    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                                            \
+    __builtin_amdgcn_sched_barrier(0);                                                            \
+    rbuf = rbuf == 2 ? 0u : rbuf + 1;                                                             \
+    wbuf = wbuf == 2 ? 0u : wbuf + 1;                                                             \
+    VK_PF_ADVANCE()                                                                               \
+  }
+
+  for (uint32_t t = 0; t < my_tiles; ++t) {
+    f32x16 acc[16];
+    VK_PF_STAGE(true, 0u, f0, f1, stg_b, stg_a)   // accumulators are born from a zero C operand
+    VK_PF_STAGE(false, 1u, f1, f0, stg_a, stg_b)
+    for (uint32_t st = 2; st < stages; st += 2) {
+      VK_PF_STAGE(false, st, f0, f1, stg_b, stg_a)
+      VK_PF_STAGE(false, st + 1, f1, f0, stg_a, stg_b)
+    }
+    // ---- tile done.  Per output register r (query (r & 3) + 8 (r >> 2) + 4 kk of the tile, this lane's entry): the 16 class
+    // sums combined with _mm512_reduce_add_ps's pairing (l, l + 8) -> (l, l + 4) -> (l, l + 2) -> (0, 1), then 1 - dot
+    const uint32_t e = (first_tile + t) * kMfmaTile + wave * 32 + li;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      float v[16];
+#pragma unroll
+      for (int l = 0; l < 16; ++l) v[l] = acc[l][r];
+#pragma unroll
+      for (int l = 0; l < 8; ++l) v[l] = v[l + 8] + v[l];
+#pragma unroll
+      for (int l = 0; l < 4; ++l) v[l] = v[l + 4] + v[l];
+      const float dot = (v[0] + v[2]) + (v[1] + v[3]);
+      const uint32_t qi = (uint32_t)((r & 3) + 8 * (r >> 2)) + 4 * kk;
+      if (qi < tq && q0 + qi < a.nq && e < a.shared_len) a.out[(size_t)(q0 + qi) * a.shared_len + e] = 1.0f - dot;
+      // keep the 16 gathers of one output register together: hoisting all 256 accumulator reads ahead of the adds would
+      // need 256 more registers and spill into the pipelined loop (K4)
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+#undef VK_PF_STAGE
+#undef VK_PF_ADVANCE
 }
 
 __global__ __launch_bounds__(256) void prefilter_select_kernel(PrefilterSelectArgs a) {
@@ -179,11 +456,36 @@ __global__ __launch_bounds__(256) void prefilter_select_kernel(PrefilterSelectAr
   if (tid == 0) a.count[q] = running;
 }
 
+// K8m's launch: the grid from the CU count and the number of query tiles -- every CU one block while there are that many row
+// tiles, and with nq <= tq every row leaves HBM once
+hipError_t launch_prefilter_mfma(const PrefilterDistArgs &a, bool bf16, hipStream_t s) {
+  uint32_t tq = prefilter_mfma_tile_q(a.row_stride_f);
+  uint32_t nqt = (a.nq + tq - 1) / tq;
+  const uint32_t n_tiles = (a.shared_len + kMfmaTile - 1) / kMfmaTile;
+  int dev = 0, cus = 0;
+  (void)hipGetDevice(&dev);
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  uint32_t nrp = std::max<uint32_t>(8, ((uint32_t)(cus > 0 ? cus : 256) / nqt) & ~7u);
+  nrp = std::min<uint32_t>(nrp, (n_tiles + 7) & ~7u);
+  if ((uint64_t)nrp * nqt > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  const size_t lds = (size_t)tq * (a.row_stride_f + 4) * 4 + kPrefilterMfmaRingBytes;
+  const void *f = bf16 ? reinterpret_cast<const void *>(&prefilter_mfma_kernel<true>) : reinterpret_cast<const void *>(&prefilter_mfma_kernel<false>);
+  hipError_t e = ensure_max_lds(f);
+  if (e != hipSuccess) return e;
+  PrefilterDistArgs args = a;
+  void *params[] = {&args, &nrp, &nqt, &tq};
+  return hipLaunchKernel(f, dim3(nrp * nqt), dim3(256), params, lds, s);
+}
+
 }  // namespace
 
 uint32_t prefilter_tiles(uint64_t entries) { return (uint32_t)((entries + kTileEntries - 1) / kTileEntries); }
 
 hipError_t launch_prefilter_distance(const PrefilterDistArgs &a, bool l2, bool bf16, hipStream_t s) {
+  // K8m: the caller's wish and the drivers' own decision function; a launch it does not take runs K8b exactly as before
+  if (prefilter_takes_mfma(a.mfma != 0, a.seg_begin == nullptr, l2, a.row_stride_f, a.nq) && a.shared_len != 0 &&
+      a.chunks * 16 == a.row_stride_f && a.q_stride_f >= a.row_stride_f)
+    return launch_prefilter_mfma(a, bf16, s);
   // shared segment: (tiles rounded up to eight) x nq blocks; CSR: the host's tile_begin[nq] = a.n_tiles
   const uint64_t blocks = a.seg_begin == nullptr ? (uint64_t)((prefilter_tiles(a.shared_len) + 7) / 8) * 8 * a.nq : a.n_tiles;
   if (blocks == 0) return hipSuccess;

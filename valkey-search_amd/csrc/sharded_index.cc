@@ -676,6 +676,20 @@ class ShardedIndex final : public Index {
     return Status::Ok();
   }
 
+  Status prefilter_mfma_stats(vk_prefilter_mfma_stats *out) override {   // every shard launches for itself: the sums
+    memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    for (auto &sh : shards_) {
+      vk_prefilter_mfma_stats t;
+      VK_TRY(sh->prefilter_mfma_stats(&t));
+      out->launches += t.launches;
+      out->queries += t.queries;
+      out->entries += t.entries;
+      out->declined += t.declined;
+    }
+    return Status::Ok();
+  }
+
   Status label_map_stats(vk_label_map_stats *out) override {   // one label map per shard: the sums
     memset(out, 0, sizeof(*out));
     out->struct_size = sizeof(*out);
