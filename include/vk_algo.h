@@ -165,6 +165,14 @@ class Algo {
     Check(vk_index_large_k_sort_stats(ix_, &s));
     return s;
   }
+  // the dense distances of the one-pass path on the matrix cores (vk_index_large_k_mfma_stats; options flat-large-k = 1 and
+  // flat-large-k-mfma = 1)
+  vk_flat_large_k_mfma_stats largeKMfmaStats() const {
+    vk_flat_large_k_mfma_stats s;
+    s.struct_size = sizeof(s);
+    Check(vk_index_large_k_mfma_stats(ix_, &s));
+    return s;
+  }
   // shared-list pre-filter distances on the matrix cores (vk_index_prefilter_mfma_stats; option prefilter-shared-mfma = 1)
   vk_prefilter_mfma_stats prefilterMfmaStats() const {
     vk_prefilter_mfma_stats s;

@@ -520,6 +520,21 @@ typedef struct vk_flat_large_k_sort_stats {
   uint64_t finish_ns;           /* ... the host's loop over the hand-back (the sort, or the copy), by the host's clock */
 } vk_flat_large_k_sort_stats;
 int vk_index_large_k_sort_stats(vk_index *ix, vk_flat_large_k_sort_stats *out);
+/* The distance pass of that search on the matrix cores, in a struct of its own (the two above keep their sizes): set struct_size
+ * = sizeof(vk_flat_large_k_mfma_stats) before the call.  With options flat-large-k = 1 and flat-large-k-mfma = 1 a chunk of
+ * queries takes its dense distances from the matrix cores when the metric is IP or COSINE, the chunk holds at least 5 queries
+ * and the row stride is a multiple of 64 floats of at most 1664; the bits are those of the vector kernel, so the answers do not
+ * change.  A chunk that does not qualify -- the last, short one of a call too -- is counted as declined and runs the vector
+ * kernel.  With flat-large-k-mfma = 0 (the default) every counter stays 0.  An HNSW index answers zeros, a sharded index the
+ * sums of its shards. */
+typedef struct vk_flat_large_k_mfma_stats {
+  uint64_t struct_size;
+  uint64_t launches;   /* chunks whose distances came from the matrix cores */
+  uint64_t queries;    /* ... and their queries */
+  uint64_t rows;       /* ... and the rows they walked (count, once per launch) */
+  uint64_t declined;   /* chunks that stayed on the vector kernel while the option was 1 */
+} vk_flat_large_k_mfma_stats;
+int vk_index_large_k_mfma_stats(vk_index *ix, vk_flat_large_k_mfma_stats *out);
 /* K8m, in a struct of its own (vk_prefilter_stats_v2 and vk_filter_exact_stats keep their sizes): set struct_size =
  * sizeof(vk_prefilter_mfma_stats) before the call.  With option prefilter-shared-mfma = 1 a pre-filter batch over a SHARED list
  * (vk_index_search_labels_batch with list_begin == NULL, every run of vk_index_search_filter_exact_batch, a collected lane of
@@ -597,7 +612,10 @@ int vk_index_search_batch_filter_handles(vk_index *ix, const void *queries, uint
  *   the labels it touched are applied to that map on the device instead of the rebuild; vk_label_map_stats),
  *   prefilter-label-map-delta-max (1 .. 1 << 24, default 65 536: a phase that touched more labels has the map rebuilt),
  *   prefilter-shared-mfma (0 / 1, read per batch, ships 0: a pre-filter batch over a shared list takes its distances from the
- *   matrix cores -- IP / COSINE, at least 5 queries, row strides up to 1664 floats; same answers; vk_prefilter_mfma_stats), ...
+ *   matrix cores -- IP / COSINE, at least 5 queries, row strides up to 1664 floats; same answers; vk_prefilter_mfma_stats),
+ *   flat-large-k-mfma (0 / 1, read per call, ships 0, no effect while flat-large-k is 0: a chunk of a FLAT search with k > 1024
+ *   takes its dense distances from the matrix cores -- IP / COSINE, at least 5 queries in the chunk, row strides that are a
+ *   multiple of 64 floats up to 1664; same answers; vk_flat_large_k_mfma_stats), ...
  * A sharded index applies an option to itself and to every shard.  Unknown name or value out of range: VK_ERR_INVALID.
  * Options take effect for searches that START after the call; no search path reads the environment. */
 int vk_index_set_option(vk_index *ix, const char *name, uint64_t value);

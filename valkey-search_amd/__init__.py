@@ -98,6 +98,12 @@ class FlatLargeKSortStats(C.Structure):
                 ("timed_chunks", C.c_uint64), ("device_ns", C.c_uint64), ("download_ns", C.c_uint64), ("finish_ns", C.c_uint64)]
 
 
+class FlatLargeKMfmaStats(C.Structure):
+    """vk_flat_large_k_mfma_stats"""
+    _fields_ = [("struct_size", C.c_uint64), ("launches", C.c_uint64), ("queries", C.c_uint64), ("rows", C.c_uint64),
+                ("declined", C.c_uint64)]
+
+
 class PrefilterMfmaStats(C.Structure):
     """vk_prefilter_mfma_stats"""
     _fields_ = [("struct_size", C.c_uint64), ("launches", C.c_uint64), ("queries", C.c_uint64), ("entries", C.c_uint64),
@@ -217,6 +223,7 @@ def lib() -> C.CDLL:
     L.vk_index_filter_exact_stats.argtypes = [vp, C.POINTER(FilterExactStats)]
     L.vk_index_large_k_stats.argtypes = [vp, C.POINTER(FlatLargeKStats)]
     L.vk_index_large_k_sort_stats.argtypes = [vp, C.POINTER(FlatLargeKSortStats)]
+    L.vk_index_large_k_mfma_stats.argtypes = [vp, C.POINTER(FlatLargeKMfmaStats)]
     L.vk_index_prefilter_mfma_stats.argtypes = [vp, C.POINTER(PrefilterMfmaStats)]
     L.vk_index_label_map_stats.argtypes = [vp, C.POINTER(LabelMapStats)]
     L.vk_index_label_map_read.argtypes = [vp, vp, vp, u64, u64p]
@@ -655,6 +662,13 @@ class Index:
         s = FlatLargeKSortStats()
         s.struct_size = C.sizeof(FlatLargeKSortStats)
         _check(lib().vk_index_large_k_sort_stats(self._h, C.byref(s)))
+        return s
+
+    def large_k_mfma_stats(self) -> FlatLargeKMfmaStats:
+        """the one-pass path's dense distances on the matrix cores (vk_index_large_k_mfma_stats; option flat-large-k-mfma)"""
+        s = FlatLargeKMfmaStats()
+        s.struct_size = C.sizeof(FlatLargeKMfmaStats)
+        _check(lib().vk_index_large_k_mfma_stats(self._h, C.byref(s)))
         return s
 
     def prefilter_mfma_stats(self) -> PrefilterMfmaStats:

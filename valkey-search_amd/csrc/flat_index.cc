@@ -887,6 +887,7 @@ class FlatIndex final : public Index {
     // and the first k entries of every query, and the host's loop is a copy
     const bool dsort = opt_.get(kOptFlatLargeKDeviceSort) != 0;
     const bool timed = opt_.get(kOptKernelTiming) != 0;   // (vk_flat_large_k_sort_stats: where a chunk's time goes)
+    const bool mfma = opt_.get(kOptFlatLargeKMfma) != 0;
     const LargeKPlan plan = dsort ? large_k_plan_sorted(nq, count, k, opt_.get(kOptFlatLargeKBytes)) : large_k_plan(nq, count, k, opt_.get(kOptFlatLargeKBytes));
     const uint64_t cap = large_k_cap(k);
     if (!plan.fits || cap > 0xFFFFFFFFull || count > 0xFFFFFFFFull || (size_t)chunks * 64 > 160 * 1024) {
@@ -956,7 +957,17 @@ class FlatIndex final : public Index {
       }
       VK_HIP_TRY(hipMemsetAsync(a.hist, 0, qc * kLargeKBins * 4, ctx->stream));
       if (timed) VK_HIP_TRY(hipEventRecord(ev0, ctx->stream));
-      VK_HIP_TRY(launch_flat_large_k_distance(a, l2(), store_.bf16(), flat_scan_pick_qb(qc, chunks, 1, l2()), ctx->stream));
+      // option flat-large-k-mfma: the chunk's distances from the matrix cores where large_k_takes_mfma agrees (the same bits), the
+      // vector kernel otherwise -- chunk by chunk: the last, short chunk of a call may be declined while the others are taken
+      LargeKMfmaCount mc;
+      if (large_k_mfma_decide(mfma, &mc, l2(), store_.stride_f(), qc, count))
+        VK_HIP_TRY(launch_flat_large_k_distance_mfma(a, store_.bf16(), ctx->stream));
+      else
+        VK_HIP_TRY(launch_flat_large_k_distance(a, l2(), store_.bf16(), flat_scan_pick_qb(qc, chunks, 1, l2()), ctx->stream));
+      lkm_.launches.fetch_add(mc.launches, std::memory_order_relaxed);
+      lkm_.queries.fetch_add(mc.queries, std::memory_order_relaxed);
+      lkm_.rows.fetch_add(mc.rows, std::memory_order_relaxed);
+      lkm_.declined.fetch_add(mc.declined, std::memory_order_relaxed);
       VK_HIP_TRY(launch_flat_large_k_select(a, ctx->stream));
       VK_HIP_TRY(launch_flat_large_k_emit(a, ctx->stream));
       if (dsort) VK_HIP_TRY(launch_flat_large_k_sort(sa, ctx->stream));
@@ -1056,6 +1067,16 @@ class FlatIndex final : public Index {
     out->device_ns = lks_.device_ns.load(std::memory_order_relaxed);
     out->download_ns = lks_.download_ns.load(std::memory_order_relaxed);
     out->finish_ns = lks_.finish_ns.load(std::memory_order_relaxed);
+    return Status::Ok();
+  }
+
+  Status large_k_mfma_stats(vk_flat_large_k_mfma_stats *out) override {
+    memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    out->launches = lkm_.launches.load(std::memory_order_relaxed);
+    out->queries = lkm_.queries.load(std::memory_order_relaxed);
+    out->rows = lkm_.rows.load(std::memory_order_relaxed);
+    out->declined = lkm_.declined.load(std::memory_order_relaxed);
     return Status::Ok();
   }
 
@@ -1636,6 +1657,10 @@ class FlatIndex final : public Index {
   struct LargeKSortCounters {
     std::atomic<uint64_t> sorted_queries{0}, merge_passes{0}, downloaded_entries{0}, timed_chunks{0}, device_ns{0}, download_ns{0}, finish_ns{0};
   } lks_;
+  // ... and of their distance launches on the matrix cores (vk_flat_large_k_mfma_stats)
+  struct LargeKMfmaCounters {
+    std::atomic<uint64_t> launches{0}, queries{0}, rows{0}, declined{0};
+  } lkm_;
   // per-call lower bounds of search_in_passes (set only around its scan() calls, under the ctx lease)
   static thread_local const float *lb_dist_;
   static thread_local const uint64_t *lb_label_;

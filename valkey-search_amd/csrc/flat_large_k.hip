@@ -13,7 +13,12 @@
 //                                the one "not a candidate" class from there on: K3 never lists a NaN distance either
 //                                (dist <= thr is false).  The waves stride over the row tiles; nothing at or beyond count is
 //                                written.
-//   flat_large_k_hist_kernel     one digit of the select: grid (slices of kLargeKSlice entries) x (queries).  The block counts
+//   flat_dense_mfma_kernel       the same matrix, bit for bit, from the matrix cores (option flat-large-k-mfma; IP / COSINE, chunks
+//                                of five or more queries, strides that are a multiple of 64 floats up to 1664 -- large_k_takes_mfma
+//                                of flat_large_k_host.hpp; everything else, L2 and a short last chunk included, stays on the
+//                                kernel above).  128 rows x 32 / 24 / 16 queries per block, v_mfma_f32_32x32x2_f32 as sixteen
+//                                k-ordered chains; described where it stands.
+//   flat_large_k_hist_kernel    one digit of the select: grid (slices of kLargeKSlice entries) x (queries).  The block counts
 //   flat_large_k_pick_kernel     the digit of every non-NaN entry whose higher digits equal the prefix chosen so far in LDS
 //                                bins and adds the bins that are not empty into hist[q][] with one vector atomicAdd each; one
 //                                wave per query then finds the bin that holds the k-th entry, extends the prefix, and clears
@@ -36,6 +41,9 @@
 #include "device_common.hpp"
 #include "flat_large_k_host.hpp"
 #include "kernels.hpp"
+#include "mfma_stage.hpp"
+
+#include <algorithm>
 
 namespace vk {
 
@@ -89,6 +97,192 @@ __global__ __launch_bounds__(256) void flat_dense_distance_kernel(FlatLargeKArgs
       if (valid && j == 0) a.dist[(size_t)(qbase + qi) * a.ld + row] = cand ? d : __builtin_nanf("");
     }
   }
+}
+
+// ---- the dense distances on the matrix cores (option flat-large-k-mfma) -----------------------------------------------------------
+// flat_dense_distance_kernel<false, kBf16>'s matrix for a chunk of five or more queries, bit for bit: K8m's arithmetic and pipeline
+// (prefilter_select.hip; the stage helpers are shared, mfma_stage.hpp) over CONTIGUOUS rows.  The f32-input MFMA is a k-ordered
+// fmaf chain: one accumulator tile per lane class l, fed (chunk c, element l), (chunk c + 1, element l), ... in order, is chain l
+// of quad_row_distance for 32 x 32 (query, row) pairs; the 16 tiles are combined with quad_reduce16's tree, then 1 - dot.
+//   block tile  = 128 rows x tq queries (prefilter_mfma_tile_q); wave w owns rows [32w, 32w + 32) of the tile; A = queries, B = rows
+//   Q tile      : resident in LDS, [tq][stride + 4] f32; rows: HBM -> registers -> the wave's private ring (3 stages of [32 rows]
+//                 [36 dwords]) -> MFMA operands, software pipeline unrolled by two, no block barrier behind the Q tile's
+//   rows        : no slot list.  A lane's four (bf16: two) 16-byte loads of a stage are at tile base + a per-lane 32-bit offset +
+//                 stage * 128 (64) bytes: the tile base is wave-uniform and moves by 128 rows at a tile boundary of the loader's
+//                 flattened (tile, stage) stream; the offsets are per-lane constants -- (row in the tile) * row bytes + piece --
+//                 except in a ragged last tile, where a row past count - 1 takes the offset of row count - 1 (re-read, not stored)
+//   mask        : lane li owns row tile * 128 + wave * 32 + li for all 16 of its output registers: its label is requested when
+//                 the tile starts and its allow bit behind the tile's first two stages, both looked at in the epilogue only, which
+//                 stores NaN or 1 - dot
+//   stores      : every output register is 32 consecutive floats of one query's row of dist, at (q0 + qi) * ld + row
+//   grid        : nrp x nqt blocks, nrp (a multiple of 8) from the CU count; a block walks a contiguous range of row tiles; the
+//                 nqt blocks of a range sit on one XCD, adjacent in dispatch order
+// Nothing at or beyond count is read or written.  Plain vector loads and stores and LDS; every loop bound is an argument.
+static_assert(kPrefilterMfmaRingBytes == 4 * kMfmaBufs * kMfmaBufFloats * 4, "prefilter_mfma_tile_q budgets this ring");
+
+struct DenseOffs { uint32_t o0, o1, o2, o3; };   // by value, like the stage sets
+
+// this lane's byte offsets from the first row of tile `tile` (< n_tiles) to the pieces it stages; at most 127 rows of at most
+// 6656 bytes: 32 bits hold them
+template <bool kBf16>
+__device__ __forceinline__ DenseOffs dense_tile_offs(uint32_t count, uint32_t tile, uint32_t wave, uint32_t lane, uint32_t row_bytes) {
+  const uint32_t lim = count - 1 - tile * kMfmaTile;   // the last row of the table, counted from the tile's first (wave-uniform)
+  const uint32_t r = wave * 32 + mfma_lane_row<kBf16>(lane);
+  const uint32_t piece = (kBf16 ? lane & 3 : lane & 7) * 16;
+  constexpr uint32_t step = kBf16 ? 16 : 8;
+  DenseOffs o;
+  o.o0 = (r < lim ? r : lim) * row_bytes + piece;
+  o.o1 = (r + step < lim ? r + step : lim) * row_bytes + piece;
+  if constexpr (kBf16) {
+    o.o2 = o.o0;
+    o.o3 = o.o0;
+  } else {
+    o.o2 = (r + 2 * step < lim ? r + 2 * step : lim) * row_bytes + piece;
+    o.o3 = (r + 3 * step < lim ? r + 3 * step : lim) * row_bytes + piece;
+  }
+  return o;
+}
+// global -> registers, one stage (2 chunks) of the wave's 32 rows: a uniform base, a 32-bit add per 16-byte load
+template <bool kBf16>
+__device__ __forceinline__ MfmaStg dense_stage_load(const char *tile_base, const DenseOffs o, uint32_t st) {
+  const uint32_t off = st * (kBf16 ? 64u : 128u);
+  MfmaStg s;
+  s.v0 = *reinterpret_cast<const float4 *>(tile_base + (o.o0 + off));
+  s.v1 = *reinterpret_cast<const float4 *>(tile_base + (o.o1 + off));
+  if constexpr (kBf16) {
+    s.v2 = s.v0;
+    s.v3 = s.v0;
+  } else {
+    s.v2 = *reinterpret_cast<const float4 *>(tile_base + (o.o2 + off));
+    s.v3 = *reinterpret_cast<const float4 *>(tile_base + (o.o3 + off));
+  }
+  return s;
+}
+
+// nrp row partitions (a multiple of 8) x nqt query tiles of tq; a.row_stride_f a multiple of 64, a.chunks = a.row_stride_f / 16
+template <bool kBf16>
+__global__ __launch_bounds__(256, 1) void flat_dense_mfma_kernel(FlatLargeKArgs a, uint32_t nrp, uint32_t nqt, uint32_t tq) {
+  extern __shared__ float4 mfma_lds[];
+  float *lds = reinterpret_cast<float *>(mfma_lds);
+  const uint32_t tid = threadIdx.x;
+  const uint32_t lane = tid & 63;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: keep it in a scalar register
+  const uint32_t li = lane & 31;   // query (A) / row (B) index inside the 32-wide MFMA tile
+  const uint32_t kk = lane >> 5;   // which of the two chunks of the stage this lane feeds
+  const uint32_t width = a.row_stride_f;
+  const uint32_t stages = width / 32;   // even: the ping-pong register sets keep their parity from tile to tile
+  const uint32_t qstride = width + 4;
+  const uint32_t row_bytes = width * (kBf16 ? 2u : 4u);
+  // blocks b and b + 8 share an XCD: the nqt blocks that walk one row range are neighbours there (K8m's and K4's dealing)
+  const uint32_t xcd = blockIdx.x & 7u, seq = blockIdx.x >> 3;
+  const uint32_t rp = (seq / nqt) * 8u + xcd;
+  const uint32_t q0 = (seq % nqt) * tq;
+  const uint32_t n_tiles = (uint32_t)(((uint64_t)a.count + kMfmaTile - 1) / kMfmaTile);
+  const uint32_t t_base = n_tiles / nrp, t_rem = n_tiles % nrp;
+  const uint32_t first_tile = rp * t_base + (rp < t_rem ? rp : t_rem);
+  const uint32_t my_tiles = t_base + (rp < t_rem ? 1u : 0u);
+  if (my_tiles == 0) return;   // (block-uniform) more partitions than tiles
+
+  float *lds_q = lds;   // [tq][qstride], read-only behind the barrier
+  float *lds_x = lds + (size_t)tq * qstride + (size_t)wave * kMfmaBufs * kMfmaBufFloats;
+  // ---- Q tile -> LDS (queries past qc replicate the last one; their results are discarded)
+  for (uint32_t i = tid; i < tq * (width / 4); i += 256) {
+    const uint32_t q = i / (width / 4), c4 = i % (width / 4);
+    const uint32_t gq = q0 + q < a.qc ? q0 + q : a.qc - 1;
+    *reinterpret_cast<float4 *>(lds_q + (size_t)q * qstride + c4 * 4) = reinterpret_cast<const float4 *>(a.queries + (size_t)gq * a.q_stride_f)[c4];
+  }
+
+  // ---- the loader's place in this block's flattened (tile, stage) stream: its tile's first row and this lane's offsets from
+  // there.  The loader never moves past the last stage of the stream: the prefetches issued behind the end re-read that stage
+  // and are not used.
+  uint32_t ld_tile = first_tile, ld_st = 0, ld_left = my_tiles * stages;   // (< 2^32: at most 2^25 tiles of at most 52 stages)
+  const size_t tile_bytes = (size_t)kMfmaTile * row_bytes;
+  const char *ld_base = static_cast<const char *>(a.rows) + (size_t)ld_tile * tile_bytes;
+  DenseOffs ro = dense_tile_offs<kBf16>(a.count, ld_tile, wave, lane, row_bytes);
+#define VK_LK_ADVANCE()                                                           \
+  if (ld_left > 1) { /* (wave-uniform, between two stages) */                     \
+    --ld_left;                                                                    \
+    if (++ld_st == stages) {                                                      \
+      ld_st = 0;                                                                  \
+      ++ld_tile;                                                                  \
+      ld_base += tile_bytes;                                                      \
+      ro = dense_tile_offs<kBf16>(a.count, ld_tile, wave, lane, row_bytes);       \
+    }                                                                             \
+  }
+  // Software pipeline over the stream, iteration i = stage i (K8m's, K4's): the global loads of stage i + 3 are issued at the top
+  // of i, written to LDS at the bottom of i + 1, read LDS -> registers during i + 2, multiplied during i + 3.  Stage s lives in
+  // ring buffer s % 3.  Unrolled by two with ping-pong register sets.
+  MfmaStg stg_a, stg_b;
+  stg_a = dense_stage_load<kBf16>(ld_base, ro, ld_st);
+  mfma_stage_store<kBf16>(lds_x, lane, stg_a);
+  VK_LK_ADVANCE()
+  stg_a = dense_stage_load<kBf16>(ld_base, ro, ld_st);
+  mfma_stage_store<kBf16>(lds_x + kMfmaBufFloats, lane, stg_a);
+  VK_LK_ADVANCE()
+  stg_a = dense_stage_load<kBf16>(ld_base, ro, ld_st);
+  stg_b = stg_a;
+  VK_LK_ADVANCE()
+  __syncthreads();   // the shared Q tile is in place
+
+  const uint32_t x_off = li * kMfmaXStride + kk * 16;
+  const float *q_row = lds_q + (size_t)(li < tq ? li : tq - 1) * qstride;
+  MfmaFrag f0 = mfma_frag_load(lds_x + x_off, q_row, 0, kk), f1 = f0;
+  uint32_t rbuf = 1;   // buffer of stage done + 1
+  uint32_t wbuf = 2;   // buffer of stage done + 2
+
+  // one iteration: F = fragments of stage ST, NF receives the next stage's, SNEW the loads of stage done + 3, SOLD (the loads
+  // of stage done + 2) goes to LDS; the memory operations are pinned between the 16 MFMAs (VK_MFMA_STAGE_SCHED)
+#define VK_LK_STAGE(ZERO, ST, F, NF, SNEW, SOLD)                                                  \
+  {                                                                                               \
+    const uint32_t nst = (ST) + 1 == stages ? 0u : (ST) + 1;                                      \
+    SNEW = dense_stage_load<kBf16>(ld_base, ro, ld_st);                                           \
+    mfma_stage_mul<ZERO>(acc, F);                                                                 \
+    NF = mfma_frag_load(lds_x + rbuf * kMfmaBufFloats + x_off, q_row, nst, kk);                   \
+    mfma_stage_store<kBf16>(lds_x + wbuf * kMfmaBufFloats, lane, SOLD);                           \
+    VK_MFMA_STAGE_SCHED()                                                                         \
+    rbuf = rbuf == 2 ? 0u : rbuf + 1;                                                             \
+    wbuf = wbuf == 2 ? 0u : wbuf + 1;                                                             \
+    VK_LK_ADVANCE()                                                                               \
+  }
+
+  for (uint32_t t = 0; t < my_tiles; ++t) {
+    // this lane's row of the tile: in the table while its place in the tile is at or below the table's last row's
+    const uint32_t lim = a.count - 1 - (first_tile + t) * kMfmaTile;
+    const uint32_t in_tile = wave * 32 + li;
+    const bool valid = in_tile <= lim;
+    const size_t row = (size_t)(first_tile + t) * kMfmaTile + (valid ? in_tile : lim);
+    const uint64_t lab = a.labels[row];   // requested now, looked at in the epilogue
+    __builtin_amdgcn_sched_barrier(0);    // (not one of the loads the first stage pins between its MFMAs)
+    f32x16 acc[16];
+    VK_LK_STAGE(true, 0u, f0, f1, stg_b, stg_a)   // accumulators are born from a zero C operand
+    VK_LK_STAGE(false, 1u, f1, f0, stg_a, stg_b)
+    const bool cand = lab != kNoLabel && allow_bit(a.allow_bits, a.allow_nbits, lab);   // (the label is here by now; the bit: epilogue)
+    for (uint32_t st = 2; st < stages; st += 2) {
+      VK_LK_STAGE(false, st, f0, f1, stg_b, stg_a)
+      VK_LK_STAGE(false, st + 1, f1, f0, stg_a, stg_b)
+    }
+    // ---- tile done.  Per output register r (query (r & 3) + 8 (r >> 2) + 4 kk of the tile, this lane's row): the 16 class
+    // sums combined with _mm512_reduce_add_ps's pairing (l, l + 8) -> (l, l + 4) -> (l, l + 2) -> (0, 1), then 1 - dot or NaN
+    float *__restrict__ out = a.dist + row;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      float v[16];
+#pragma unroll
+      for (int l = 0; l < 16; ++l) v[l] = acc[l][r];
+#pragma unroll
+      for (int l = 0; l < 8; ++l) v[l] = v[l + 8] + v[l];
+#pragma unroll
+      for (int l = 0; l < 4; ++l) v[l] = v[l + 4] + v[l];
+      const float dot = (v[0] + v[2]) + (v[1] + v[3]);
+      const uint32_t qi = (uint32_t)((r & 3) + 8 * (r >> 2)) + 4 * kk;
+      if (qi < tq && q0 + qi < a.qc && valid) out[(size_t)(q0 + qi) * a.ld] = cand ? 1.0f - dot : __builtin_nanf("");
+      // keep the 16 gathers of one output register together: hoisting all 256 accumulator reads ahead of the adds would
+      // need 256 more registers and spill into the pipelined loop (K4)
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+#undef VK_LK_STAGE
+#undef VK_LK_ADVANCE
 }
 
 // the thread's entry u of the block's slice: index, or count and beyond = none
@@ -527,6 +721,43 @@ hipError_t launch_flat_large_k_distance(const FlatLargeKArgs &a, bool l2, bool b
   uint32_t qb_arg = (uint32_t)qb;
   void *params[] = {&args, &qb_arg};
   return hipLaunchKernel(f, dim3(blocks, nqg), dim3(256), params, lds, s);
+}
+
+// the matrix-core launch's grid: every CU one block while there are that many row tiles, and with qc <= tq every row leaves HBM
+// once (K8m's rule)
+static void dense_mfma_grid(uint32_t count, uint32_t stride_f, uint32_t qc, uint32_t *nrp, uint32_t *nqt, uint32_t *tq) {
+  *tq = prefilter_mfma_tile_q(stride_f);
+  *nqt = (qc + *tq - 1) / *tq;
+  const uint32_t n_tiles = (uint32_t)(((uint64_t)count + kMfmaTile - 1) / kMfmaTile);
+  int dev = 0, cus = 0;
+  (void)hipGetDevice(&dev);
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  *nrp = std::max<uint32_t>(8, ((uint32_t)(cus > 0 ? cus : 256) / *nqt) & ~7u);
+  *nrp = std::min<uint32_t>(*nrp, (n_tiles + 7) & ~7u);
+}
+
+uint32_t flat_large_k_mfma_row_partitions(uint32_t count, uint32_t stride_f, uint32_t qc) {
+  if (count == 0 || !large_k_takes_mfma(true, false, stride_f, qc)) return 0;
+  uint32_t nrp, nqt, tq;
+  dense_mfma_grid(count, stride_f, qc, &nrp, &nqt, &tq);
+  return nrp;
+}
+
+hipError_t launch_flat_large_k_distance_mfma(const FlatLargeKArgs &a, bool bf16, hipStream_t s) {
+  if (!large_k_args_ok(a) || !a.rows || !a.labels || !a.queries || a.chunks == 0 || a.chunks * 16 != a.row_stride_f || a.q_stride_f < a.row_stride_f ||
+      !large_k_takes_mfma(true, false, a.row_stride_f, a.qc))
+    return hipErrorInvalidValue;
+  uint32_t nrp, nqt, tq;
+  dense_mfma_grid(a.count, a.row_stride_f, a.qc, &nrp, &nqt, &tq);
+  const size_t lds = (size_t)tq * (a.row_stride_f + 4) * 4 + kPrefilterMfmaRingBytes;
+  const void *f = bf16 ? reinterpret_cast<const void *>(&flat_dense_mfma_kernel<true>) : reinterpret_cast<const void *>(&flat_dense_mfma_kernel<false>);
+  hipError_t e = ensure_max_lds(f);
+  if (e != hipSuccess) return e;
+  e = ensure_scratch(f, s);   // (no scratch as built; a build that spills is refused where the device cannot hold it)
+  if (e != hipSuccess) return e;
+  FlatLargeKArgs args = a;
+  void *params[] = {&args, &nrp, &nqt, &tq};
+  return hipLaunchKernel(f, dim3(nrp * nqt), dim3(256), params, lds, s);
 }
 
 hipError_t launch_flat_large_k_select(const FlatLargeKArgs &a, hipStream_t s) {

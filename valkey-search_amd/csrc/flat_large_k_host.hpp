@@ -8,6 +8,8 @@
 #include <algorithm>
 #include <vector>
 
+#include "prefilter_host.hpp"   // (host-only too: K8m's limits, which the matrix-core distance pass shares)
+
 namespace vk {
 
 // Entries the device hands back per query: the k-th key's tie group may reach past k, so the list has room for `slack` more.
@@ -67,6 +69,32 @@ inline uint64_t large_k_sorted_list_bytes(uint64_t k) { return (2 * large_k_cap(
 // large_k_plan with those bytes per query instead of the one list (same rules otherwise)
 inline LargeKPlan large_k_plan_sorted(uint64_t nq, uint64_t count, uint64_t k, uint64_t budget_bytes) {
   return large_k_plan_lists(nq, count, large_k_sorted_list_bytes(k), budget_bytes);
+}
+
+// ---- the dense distances of a chunk on the matrix cores (option flat-large-k-mfma; flat_dense_mfma_kernel in flat_large_k.hip) ----
+// One decision, asked by FlatIndex::search_large_k for every chunk (what vk_flat_large_k_mfma_stats counts) and by
+// launch_flat_large_k_distance_mfma (what it refuses), so the two cannot disagree.  The limits are K8m's, from the same LDS
+// budget: IP / COSINE (L2 is not a product of the inputs), at least kPrefilterMfmaMinQueries queries in the chunk, a stride
+// prefilter_mfma_tile_q can hold (a multiple of 64 floats, at most 1664).  The last, short chunk of a call may be declined
+// while the others are taken.
+inline bool large_k_takes_mfma(bool wanted, bool l2, uint64_t stride_f, uint64_t qc) {
+  return wanted && !l2 && qc >= kPrefilterMfmaMinQueries && prefilter_mfma_tile_q(stride_f) != 0;
+}
+// what a call did with its chunks (vk_flat_large_k_mfma_stats); the index folds it into its atomics
+struct LargeKMfmaCount {
+  uint64_t launches = 0, queries = 0, rows = 0, declined = 0;
+};
+// the decision for one chunk of qc queries over count rows, counted: true = the matrix-core kernel runs
+inline bool large_k_mfma_decide(bool wanted, LargeKMfmaCount *c, bool l2, uint64_t stride_f, uint64_t qc, uint64_t count) {
+  if (!wanted) return false;
+  if (!large_k_takes_mfma(true, l2, stride_f, qc)) {
+    ++c->declined;
+    return false;
+  }
+  ++c->launches;
+  c->queries += qc;
+  c->rows += count;
+  return true;
 }
 
 // order-preserving u32 of a non-NaN float, -0 and +0 sharing a key: merge_key of flat_scan.hip

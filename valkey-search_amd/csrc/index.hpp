@@ -271,6 +271,12 @@ class Index {
     out->struct_size = sizeof(*out);
     return Status::Ok();
   }
+  // vk_index_large_k_mfma_stats (as large_k_stats)
+  virtual Status large_k_mfma_stats(vk_flat_large_k_mfma_stats *out) {
+    memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    return Status::Ok();
+  }
   // vk_index_prefilter_mfma_stats (a sharded index sums its shards)
   virtual Status prefilter_mfma_stats(vk_prefilter_mfma_stats *out) {
     memset(out, 0, sizeof(*out));

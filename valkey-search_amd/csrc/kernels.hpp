@@ -638,6 +638,12 @@ struct FlatLargeKArgs {
 uint32_t flat_large_k_slice();         // entries one block of the histogram / emit launches covers
 uint32_t flat_large_k_dist_blocks();   // most row blocks of the distance launch (its waves stride over the row tiles)
 hipError_t launch_flat_large_k_distance(const FlatLargeKArgs &a, bool l2, bool bf16, int qb, hipStream_t s);
+// ... the same dist[q][row] from the matrix cores (flat_dense_mfma_kernel; option flat-large-k-mfma), IP / COSINE only: the bits
+// of launch_flat_large_k_distance(a, false, bf16, ...), NaN in the same places, nothing at or beyond count read or written.
+// hipErrorInvalidValue for arguments large_k_takes_mfma (flat_large_k_host.hpp) does not take.  flat_large_k_mfma_row_partitions:
+// the row partitions that launch's grid has for such a chunk (0 = not taken), each a contiguous range of 128-row tiles.
+hipError_t launch_flat_large_k_distance_mfma(const FlatLargeKArgs &a, bool bf16, hipStream_t s);
+uint32_t flat_large_k_mfma_row_partitions(uint32_t count, uint32_t stride_f, uint32_t qc);
 hipError_t launch_flat_large_k_select(const FlatLargeKArgs &a, hipStream_t s);
 hipError_t launch_flat_large_k_emit(const FlatLargeKArgs &a, hipStream_t s);
 // ... and behind the emit (option flat-large-k-device-sort): every query's n = n_less + n_eq emitted entries ordered by

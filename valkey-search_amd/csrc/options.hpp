@@ -59,6 +59,8 @@ enum OptId : uint32_t {
   kOptFlatL2Image,
   // ---- batched pre-filter search: a shared list's distances on the matrix cores (K8m) ------------------------------------------
   kOptPrefilterSharedMfma,
+  // ---- FLAT k > 1024 in one row pass: a chunk's dense distances on the matrix cores ---------------------------------------------
+  kOptFlatLargeKMfma,
   kOptCount
 };
 
@@ -167,6 +169,12 @@ inline const OptDesc &opt_desc(uint32_t id) {
       // tile); L2, per-query lists, shorter chunks and strides K8m cannot hold run K8b as before.  Read per batch.  Ships off: it
       // goes on by default only once scripts/prefilter_mfma_probe.py shows no point below the option-off median
       {"prefilter-shared-mfma", nullptr, 0, 0, 1},
+      // flat-large-k = 1, IP / COSINE, at least 5 queries in the chunk: the chunk's dense distances come from
+      // flat_dense_mfma_kernel (flat_large_k.hip: v_mfma_f32_32x32x2_f32 over contiguous rows, the bits of the vector kernel)
+      // instead of one walk over a row tile per query; L2, shorter chunks (the last one of a call too) and strides the kernel
+      // cannot hold run the vector kernel as before.  Read per call, nothing changes while flat-large-k is 0.  Ships off: it goes
+      // on by default only once scripts/flat_large_k_mfma_probe.py shows no point below the option-off median
+      {"flat-large-k-mfma", nullptr, 0, 0, 1},
   };
   return t[id];
 }

@@ -676,6 +676,20 @@ class ShardedIndex final : public Index {
     return Status::Ok();
   }
 
+  Status large_k_mfma_stats(vk_flat_large_k_mfma_stats *out) override {   // ... and its own distance launches: the sums
+    memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    for (auto &sh : shards_) {
+      vk_flat_large_k_mfma_stats t;
+      VK_TRY(sh->large_k_mfma_stats(&t));
+      out->launches += t.launches;
+      out->queries += t.queries;
+      out->rows += t.rows;
+      out->declined += t.declined;
+    }
+    return Status::Ok();
+  }
+
   Status prefilter_mfma_stats(vk_prefilter_mfma_stats *out) override {   // every shard launches for itself: the sums
     memset(out, 0, sizeof(*out));
     out->struct_size = sizeof(*out);
