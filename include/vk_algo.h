@@ -173,6 +173,13 @@ class Algo {
     Check(vk_index_large_k_mfma_stats(ix_, &s));
     return s;
   }
+  // L2 batches answered by the matrix-core bound and exact distances behind it (vk_index_l2_gemm_stats; option flat-l2-gemm = 1)
+  vk_flat_l2_gemm_stats l2GemmStats() const {
+    vk_flat_l2_gemm_stats s;
+    s.struct_size = sizeof(s);
+    Check(vk_index_l2_gemm_stats(ix_, &s));
+    return s;
+  }
   // shared-list pre-filter distances on the matrix cores (vk_index_prefilter_mfma_stats; option prefilter-shared-mfma = 1)
   vk_prefilter_mfma_stats prefilterMfmaStats() const {
     vk_prefilter_mfma_stats s;

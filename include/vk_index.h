@@ -535,6 +535,24 @@ typedef struct vk_flat_large_k_mfma_stats {
   uint64_t declined;   /* chunks that stayed on the vector kernel while the option was 1 */
 } vk_flat_large_k_mfma_stats;
 int vk_index_large_k_mfma_stats(vk_index *ix, vk_flat_large_k_mfma_stats *out);
+/* K4e, in a struct of its own (vk_index_params and vk_index_stats keep their sizes): set struct_size =
+ * sizeof(vk_flat_l2_gemm_stats) before the call.  With option flat-l2-gemm = 1 an L2 batch that the candidate filter does not
+ * take -- an index below filter-min-rows, 5 .. 32 queries, flat-filter = 0 -- and that holds at least 5 queries, with k <= 256
+ * and a row stride of at most 1856 floats, is answered by flat_l2_gemm_kernel: one f32 GEMM on the matrix cores bounds every
+ * pair's distance from below, and only the pairs the bound cannot rule out get the exact distance, with the bits of the scan
+ * kernel, so the answers do not change.  An L2 batch that does not qualify (fewer queries, k > 256, a wider stride, a pass of
+ * the k > 1024 pager, a cancelled call, flat-force-scan) is counted as declined and runs the scan kernel.  With flat-l2-gemm =
+ * 0 (the default) every counter stays 0.  The call waits for the device: `evaluated` is counted there.  An HNSW index answers
+ * zeros, a sharded index the sums of its shards. */
+typedef struct vk_flat_l2_gemm_stats {
+  uint64_t struct_size;
+  uint64_t launches;    /* batches answered by the matrix-core kernel */
+  uint64_t queries;     /* ... and their queries */
+  uint64_t rows;        /* ... and the rows they walked (count, once per batch) */
+  uint64_t evaluated;   /* (row, query) pairs that passed the gate and got an exact distance, the pre-pass's included */
+  uint64_t declined;    /* L2 batches that stayed on the scan kernel while the option was 1 */
+} vk_flat_l2_gemm_stats;
+int vk_index_l2_gemm_stats(vk_index *ix, vk_flat_l2_gemm_stats *out);
 /* K8m, in a struct of its own (vk_prefilter_stats_v2 and vk_filter_exact_stats keep their sizes): set struct_size =
  * sizeof(vk_prefilter_mfma_stats) before the call.  With option prefilter-shared-mfma = 1 a pre-filter batch over a SHARED list
  * (vk_index_search_labels_batch with list_begin == NULL, every run of vk_index_search_filter_exact_batch, a collected lane of
@@ -615,7 +633,10 @@ int vk_index_search_batch_filter_handles(vk_index *ix, const void *queries, uint
  *   matrix cores -- IP / COSINE, at least 5 queries, row strides up to 1664 floats; same answers; vk_prefilter_mfma_stats),
  *   flat-large-k-mfma (0 / 1, read per call, ships 0, no effect while flat-large-k is 0: a chunk of a FLAT search with k > 1024
  *   takes its dense distances from the matrix cores -- IP / COSINE, at least 5 queries in the chunk, row strides that are a
- *   multiple of 64 floats up to 1664; same answers; vk_flat_large_k_mfma_stats), ...
+ *   multiple of 64 floats up to 1664; same answers; vk_flat_large_k_mfma_stats),
+ *   flat-l2-gemm (0 / 1, read per call, ships 0: an L2 batch of at least 5 queries that the candidate filter does not take is
+ *   answered by a matrix-core bound and exact distances for the pairs it leaves -- k <= 256, row strides up to 1856 floats; same
+ *   answers; vk_flat_l2_gemm_stats), ...
  * A sharded index applies an option to itself and to every shard.  Unknown name or value out of range: VK_ERR_INVALID.
  * Options take effect for searches that START after the call; no search path reads the environment. */
 int vk_index_set_option(vk_index *ix, const char *name, uint64_t value);

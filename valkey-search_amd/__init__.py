@@ -104,6 +104,12 @@ class FlatLargeKMfmaStats(C.Structure):
                 ("declined", C.c_uint64)]
 
 
+class FlatL2GemmStats(C.Structure):
+    """vk_flat_l2_gemm_stats"""
+    _fields_ = [("struct_size", C.c_uint64), ("launches", C.c_uint64), ("queries", C.c_uint64), ("rows", C.c_uint64),
+                ("evaluated", C.c_uint64), ("declined", C.c_uint64)]
+
+
 class PrefilterMfmaStats(C.Structure):
     """vk_prefilter_mfma_stats"""
     _fields_ = [("struct_size", C.c_uint64), ("launches", C.c_uint64), ("queries", C.c_uint64), ("entries", C.c_uint64),
@@ -224,6 +230,7 @@ def lib() -> C.CDLL:
     L.vk_index_large_k_stats.argtypes = [vp, C.POINTER(FlatLargeKStats)]
     L.vk_index_large_k_sort_stats.argtypes = [vp, C.POINTER(FlatLargeKSortStats)]
     L.vk_index_large_k_mfma_stats.argtypes = [vp, C.POINTER(FlatLargeKMfmaStats)]
+    L.vk_index_l2_gemm_stats.argtypes = [vp, C.POINTER(FlatL2GemmStats)]
     L.vk_index_prefilter_mfma_stats.argtypes = [vp, C.POINTER(PrefilterMfmaStats)]
     L.vk_index_label_map_stats.argtypes = [vp, C.POINTER(LabelMapStats)]
     L.vk_index_label_map_read.argtypes = [vp, vp, vp, u64, u64p]
@@ -669,6 +676,13 @@ class Index:
         s = FlatLargeKMfmaStats()
         s.struct_size = C.sizeof(FlatLargeKMfmaStats)
         _check(lib().vk_index_large_k_mfma_stats(self._h, C.byref(s)))
+        return s
+
+    def l2_gemm_stats(self) -> FlatL2GemmStats:
+        """L2 batches answered by the matrix-core bound and exact distances behind it (vk_index_l2_gemm_stats; option flat-l2-gemm)"""
+        s = FlatL2GemmStats()
+        s.struct_size = C.sizeof(FlatL2GemmStats)
+        _check(lib().vk_index_l2_gemm_stats(self._h, C.byref(s)))
         return s
 
     def prefilter_mfma_stats(self) -> PrefilterMfmaStats:

@@ -23,6 +23,7 @@
 #include <queue>
 #include <thread>
 
+#include "flat_l2_gemm_host.hpp"
 #include "flat_large_k_host.hpp"
 #include "index.hpp"
 
@@ -265,6 +266,7 @@ class FlatIndex final : public Index {
     d_hn16_.release();
     d_tile_norm_.release();
     d_rows16_.release();
+    d_l2g_evaluated_.release();
   }
 
   Status add(uint64_t label, const float *row) override {
@@ -738,6 +740,21 @@ class FlatIndex final : public Index {
       if (!d_cancel) VK_TRY(ctx->arm_cancel(cancel, &d_cancel));
       return scan_gemm(ctx, d_q, nq, k, count, d_allow, allow_nbits, d_out_d, d_out_l, d_out_n, s, out_ld, d_cancel);
     }
+    // K4e (option flat-l2-gemm): the same batches under L2 -- a bound from the matrix cores, exact distances for what it leaves
+    if (l2_gemm_wanted_ != 0 && l2()) {
+      L2GemmCount c;
+      const L2GemmBatch b{true, lb_dist_ != nullptr, cancel_raised(cancel), force_scan_ != 0, nq, store_.stride_f(), k};
+      const bool take = l2_gemm_decide(true, &c, b, count);
+      l2g_.launches.fetch_add(c.launches, std::memory_order_relaxed);
+      l2g_.queries.fetch_add(c.queries, std::memory_order_relaxed);
+      l2g_.rows.fetch_add(c.rows, std::memory_order_relaxed);
+      l2g_.declined.fetch_add(c.declined, std::memory_order_relaxed);
+      if (take) {
+        const uint32_t *d_cancel = cancel_word;
+        if (!d_cancel) VK_TRY(ctx->arm_cancel(cancel, &d_cancel));
+        return scan_l2_gemm(ctx, d_q, nq, k, count, d_allow, allow_nbits, d_out_d, d_out_l, d_out_n, s, out_ld, d_cancel);
+      }
+    }
     const uint32_t *d_cancel = cancel_word;
     uint64_t row_end = count;
     if (cancel_raised(cancel)) row_end = std::min<uint64_t>(count, k);          // (those rows are scanned whatever the flag says)
@@ -1077,6 +1094,108 @@ class FlatIndex final : public Index {
     out->queries = lkm_.queries.load(std::memory_order_relaxed);
     out->rows = lkm_.rows.load(std::memory_order_relaxed);
     out->declined = lkm_.declined.load(std::memory_order_relaxed);
+    return Status::Ok();
+  }
+
+  Status l2_gemm_stats(vk_flat_l2_gemm_stats *out) override {
+    memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    out->launches = l2g_.launches.load(std::memory_order_relaxed);
+    out->queries = l2g_.queries.load(std::memory_order_relaxed);
+    out->rows = l2g_.rows.load(std::memory_order_relaxed);
+    out->declined = l2g_.declined.load(std::memory_order_relaxed);
+    const void *word;
+    {
+      std::lock_guard<std::mutex> g(l2g_mu_);   // (held for the pointer only: a first launch is never kept waiting by a poll)
+      word = d_l2g_evaluated_.p;
+    }
+    if (word != nullptr) {   // the gate counter lives on the device: every launch enqueued so far is waited for
+      (void)hipSetDevice(store_.device());
+      unsigned long long v = 0;
+      VK_HIP_TRY(hipDeviceSynchronize());
+      VK_HIP_TRY(hipMemcpy(&v, word, sizeof v, hipMemcpyDeviceToHost));
+      out->evaluated = v;
+    }
+    return Status::Ok();
+  }
+
+  // K4e launch (flat_l2_gemm.hip), laid out like scan_gemm: a pre-pass with the same kernel over the first rows of a large
+  // index, its k-th best distances as the seed of the shared bounds, nrp row partitions x nqt query tiles, one list per (block,
+  // wave, query) for the merge
+  Status scan_l2_gemm(SearchCtx *ctx, const float *d_q, uint64_t nq, uint64_t k, uint64_t count, const uint64_t *d_allow,
+                      uint64_t allow_nbits, float *d_out_d, uint64_t *d_out_l, uint32_t *d_out_n, hipStream_t s, uint64_t out_ld = 0,
+                      const uint32_t *d_cancel = nullptr) {
+    if (out_ld == 0) out_ld = k;
+    {
+      std::lock_guard<std::mutex> g(l2g_mu_);
+      if (d_l2g_evaluated_.p == nullptr) {
+        DevBuf w;   // cleared on the store's stream and waited for there alone, published only then
+        VK_TRY(w.ensure(8));
+        hipError_t e = hipMemsetAsync(w.p, 0, 8, store_.stream());
+        if (e == hipSuccess) e = hipStreamSynchronize(store_.stream());
+        if (e != hipSuccess) {
+          w.release();
+          VK_HIP_TRY(e);
+        }
+        d_l2g_evaluated_ = w;
+      }
+    }
+    const float *init_bound = nullptr;
+    const uint64_t pre_rows = gemm_prepass_rows_ * ((k + 9) / 10);
+    if (pre_rows && count >= 8 * pre_rows && !in_prepass_) {
+      in_prepass_ = true;   // the same kernel over the first rows only
+      Status ps = scan_l2_gemm(ctx, d_q, nq, k, pre_rows, d_allow, allow_nbits, d_out_d, d_out_l, d_out_n, s);
+      in_prepass_ = false;
+      VK_TRY(ps);
+      VK_TRY(ctx->d_stats.ensure(std::max<size_t>(32, nq * 8)));
+      VK_HIP_TRY(launch_kth_bound(d_out_d, d_out_n, (uint32_t)k, (uint32_t)nq, ctx->d_stats.as<float>(), s));
+      init_bound = ctx->d_stats.as<float>();
+    }
+    FlatL2GemmArgs g{};
+    g.rows = store_.d_rows();
+    g.bf16 = store_.bf16() ? 1 : 0;
+    g.labels = store_.d_labels();
+    g.queries = d_q;
+    g.allow_bits = d_allow;
+    g.allow_nbits = allow_nbits;
+    g.row_stride_f = g.q_stride_f = store_.stride_f();
+    g.chunks = store_.stride_f() / 16;
+    g.n_rows = (uint32_t)count;
+    g.nq = (uint32_t)nq;
+    g.k = (uint32_t)k;
+    g.tile_q = flat_l2_gemm_tile_q(store_.stride_f());
+    g.nqt = (uint32_t)((nq + g.tile_q - 1) / g.tile_q);
+    const uint32_t tiles = (uint32_t)((count + kL2GemmRows - 1) / kL2GemmRows);
+    uint32_t nrp = std::max<uint32_t>(8, (256 / g.nqt) & ~7u);
+    nrp = std::min<uint32_t>(nrp, std::max<uint32_t>(8, (tiles + 7) & ~7u));
+    g.nrp = nrp;
+    const uint64_t per_q = (uint64_t)nrp * 4 * k;
+    VK_TRY(ctx->d_part_d.ensure((size_t)nq * per_q * 4));
+    VK_TRY(ctx->d_part_l.ensure((size_t)nq * per_q * 8));
+    g.part_dist = ctx->d_part_d.as<float>();
+    g.part_label = ctx->d_part_l.as<uint64_t>();
+    g.evaluated = d_l2g_evaluated_.as<unsigned long long>();
+    g.cancel = in_prepass_ ? nullptr : d_cancel;
+    VK_TRY(ctx->d_sync.ensure(nq * 4));
+    g.qbound = ctx->d_sync.as<uint32_t>();
+    if (init_bound)   // (launch_kth_bound leaves the bounds' order-preserving keys behind the floats)
+      VK_HIP_TRY(hipMemcpyAsync(g.qbound, reinterpret_cast<const uint32_t *>(init_bound) + nq, nq * 4, hipMemcpyDeviceToDevice, s));
+    else
+      VK_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(g.qbound), (int)0xFF800000u, nq, s));   // key of +inf
+    VK_HIP_TRY(launch_flat_l2_gemm(g, s));
+    MergeArgs m{};
+    m.in_dist = g.part_dist;
+    m.in_label = g.part_label;
+    m.part_stride = nq * per_q;
+    m.q_stride = per_q;
+    m.parts = 1;
+    m.per_part = (uint32_t)per_q;
+    m.k = (uint32_t)k;
+    m.out_ld = (uint32_t)(in_prepass_ ? k : out_ld);
+    m.out_dist = d_out_d;
+    m.out_label = d_out_l;
+    m.out_n = d_out_n;
+    VK_HIP_TRY(launch_merge_topk(m, flat_scan_slots_per_lane(k), nq, s));
     return Status::Ok();
   }
 
@@ -1661,6 +1780,13 @@ class FlatIndex final : public Index {
   struct LargeKMfmaCounters {
     std::atomic<uint64_t> launches{0}, queries{0}, rows{0}, declined{0};
   } lkm_;
+  // ... and of the L2 batches that asked for K4e (vk_flat_l2_gemm_stats); the pairs that passed its gate are counted on the device
+  struct L2GemmCounters {
+    std::atomic<uint64_t> launches{0}, queries{0}, rows{0}, declined{0};
+  } l2g_;
+  DevBuf d_l2g_evaluated_;   // [1] unsigned long long (allocated by the first launch, under l2g_mu_)
+  std::mutex l2g_mu_;
+  OptRef l2_gemm_wanted_{&opt_, kOptFlatL2Gemm};
   // per-call lower bounds of search_in_passes (set only around its scan() calls, under the ctx lease)
   static thread_local const float *lb_dist_;
   static thread_local const uint64_t *lb_label_;

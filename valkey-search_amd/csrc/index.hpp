@@ -277,6 +277,12 @@ class Index {
     out->struct_size = sizeof(*out);
     return Status::Ok();
   }
+  // vk_index_l2_gemm_stats (as large_k_stats)
+  virtual Status l2_gemm_stats(vk_flat_l2_gemm_stats *out) {
+    memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    return Status::Ok();
+  }
   // vk_index_prefilter_mfma_stats (a sharded index sums its shards)
   virtual Status prefilter_mfma_stats(vk_prefilter_mfma_stats *out) {
     memset(out, 0, sizeof(*out));

@@ -296,6 +296,35 @@ uint32_t flat_gemm_tile_q(uint32_t row_stride_f);
 bool flat_gemm_supported(uint32_t row_stride_f, uint64_t k);
 hipError_t launch_flat_gemm(const FlatGemmArgs &a, hipStream_t s);
 
+// K4e (flat_l2_gemm.hip; option flat-l2-gemm): exact batched FLAT search under L2.  The dense work is one plain f32 GEMM on the
+// matrix cores that BOUNDS every pair's distance from below; only the pairs the bound cannot rule out get the exact
+// SimSIMD-order distance (quad_row_distance), so the answers carry K3's bits.
+struct FlatL2GemmArgs {
+  const void *rows;           // f32 or (bf16 = 1) bf16 rows, row_stride_f ELEMENTS apart
+  uint32_t bf16;
+  const uint64_t *labels;
+  const float *queries;       // [nq][q_stride_f] padded
+  const uint64_t *allow_bits;
+  uint64_t allow_nbits;
+  float *part_dist;           // [nq][nrp][4][k] one partial list per (block, wave, query)
+  uint64_t *part_label;
+  uint32_t row_stride_f, q_stride_f, chunks;
+  uint32_t n_rows, nq, k;     // n_rows >= 1
+  uint32_t nrp;               // row partitions, multiple of 8: each a contiguous range of 256-row tiles
+  uint32_t nqt;               // query tiles of tile_q
+  uint32_t tile_q;            // queries per block: 64, 32, 24 or 16 (flat_l2_gemm_tile_q)
+  // per-query pruning bound shared by every list of the launch, as FlatGemmArgs::qbound: seeded by the host with the key of
+  // +inf or of a valid upper bound of the query's k-th best distance (pre-pass), lowered by every list that fills
+  uint32_t *qbound;           // [nq]
+  unsigned long long *evaluated;   // optional [1]: += the pairs that passed the gate, once per block
+  const uint32_t *cancel;     // optional, as FlatScanArgs::cancel (polled every kCancelPollTiles 256-row tiles)
+  const uint32_t *run_flag;   // as FlatScanArgs::run_flag
+  uint32_t run_if, run_hi;
+};
+uint32_t flat_l2_gemm_tile_q(uint32_t row_stride_f);
+bool flat_l2_gemm_supported(uint32_t row_stride_f, uint64_t k);
+hipError_t launch_flat_l2_gemm(const FlatL2GemmArgs &a, hipStream_t s);
+
 struct MergeArgs {
   const float *in_dist;       // entry (part, q, i) at part*part_stride + q*q_stride + i
   const uint64_t *in_label;

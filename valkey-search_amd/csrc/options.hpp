@@ -61,6 +61,8 @@ enum OptId : uint32_t {
   kOptPrefilterSharedMfma,
   // ---- FLAT k > 1024 in one row pass: a chunk's dense distances on the matrix cores ---------------------------------------------
   kOptFlatLargeKMfma,
+  // ---- FLAT under L2, batches the candidate filter does not take: a bound from the matrix cores, exact distances behind it (K4e) ----
+  kOptFlatL2Gemm,
   kOptCount
 };
 
@@ -175,6 +177,13 @@ inline const OptDesc &opt_desc(uint32_t id) {
       // cannot hold run the vector kernel as before.  Read per call, nothing changes while flat-large-k is 0.  Ships off: it goes
       // on by default only once scripts/flat_large_k_mfma_probe.py shows no point below the option-off median
       {"flat-large-k-mfma", nullptr, 0, 0, 1},
+      // L2 batches of at least 5 queries that the candidate filter does not take (an index below filter-min-rows, 5 .. 32
+      // queries, flat-filter = 0): flat_l2_gemm_kernel (flat_l2_gemm.hip) bounds every pair's distance from below with one f32 GEMM
+      // on the matrix cores and gives the exact SimSIMD-order distance only to the pairs the bound cannot rule out -- K3's bits --
+      // instead of K3 for every pair; fewer queries, k > 256, strides beyond 1856 floats, the k > 1024 pager and IP / COSINE run
+      // what they ran before.  Read per call.  Ships off: it goes on by default only once scripts/flat_l2_gemm_probe.py shows no
+      // point below the option-off median
+      {"flat-l2-gemm", nullptr, 0, 0, 1},
   };
   return t[id];
 }

@@ -690,6 +690,21 @@ class ShardedIndex final : public Index {
     return Status::Ok();
   }
 
+  Status l2_gemm_stats(vk_flat_l2_gemm_stats *out) override {   // every shard launches for itself: the sums
+    memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    for (auto &sh : shards_) {
+      vk_flat_l2_gemm_stats t;
+      VK_TRY(sh->l2_gemm_stats(&t));
+      out->launches += t.launches;
+      out->queries += t.queries;
+      out->rows += t.rows;
+      out->evaluated += t.evaluated;
+      out->declined += t.declined;
+    }
+    return Status::Ok();
+  }
+
   Status prefilter_mfma_stats(vk_prefilter_mfma_stats *out) override {   // every shard launches for itself: the sums
     memset(out, 0, sizeof(*out));
     out->struct_size = sizeof(*out);

@@ -808,6 +808,13 @@ int vk_index_large_k_mfma_stats(vk_index *ix, vk_flat_large_k_mfma_stats *out) {
   return guarded([&] { return ix->impl->large_k_mfma_stats(out); });
 }
 
+int vk_index_l2_gemm_stats(vk_index *ix, vk_flat_l2_gemm_stats *out) {
+  if (!out) return fail(VK_ERR_INVALID, "out is NULL");
+  if (out->struct_size != sizeof(vk_flat_l2_gemm_stats)) return fail(VK_ERR_INVALID, "vk_flat_l2_gemm_stats.struct_size mismatch");
+  VK_NEED(ix);
+  return guarded([&] { return ix->impl->l2_gemm_stats(out); });
+}
+
 int vk_index_prefilter_mfma_stats(vk_index *ix, vk_prefilter_mfma_stats *out) {
   if (!out) return fail(VK_ERR_INVALID, "out is NULL");
   if (out->struct_size != sizeof(vk_prefilter_mfma_stats)) return fail(VK_ERR_INVALID, "vk_prefilter_mfma_stats.struct_size mismatch");
