@@ -60,7 +60,8 @@
 //            of three stages, no registers and no LDS store instructions in between (kBDma)
 // so HBM traffic is the row bytes and L2 traffic twice that (PMC: TCC misses 30.8 GB, hits 30.8 GB per launch).
 // bf16 rows in the inner-product space (kBfMma, kDma): rows and queries stay bf16, the bf16 matrix-core instruction
-// multiplies (query rounding 2^-8 in the margin), and the ROWS go HBM -> LDS by DMA (swizzled 128-B rows, ring of five).
+// multiplies (query rounding 2^-8 in the margin), and the ROWS go HBM -> LDS by DMA (swizzled 128-B rows, ring of five; with
+// the B operands by DMA beside them, FlatFilterArgs::bdma == 2, rings of three row stages and three B stages).
 // Roofline: HBM (30.72 GB per launch at 10M x 768 f32).  The matrix cores: 3.9 PFLOP of f16 per launch; their stream alone
 // (no operands fetched, no gate) takes 2.3-2.4 ms of a 5.1-5.2 ms launch at the clock the chip sustains under it --
 // scripts/filter_ablate.py and DESIGN.md section 5 have the whole ablation matrix (VK_FILTER_ABLATE below).
@@ -815,6 +816,11 @@ constexpr uint32_t kDmaStageBytes = kFTileRows * 128;
 // and no registers, no LDS store instructions (which were most of what the B operands cost a stage: the VGPR -> LDS path
 // moves ~80 B per clock, 410 clocks for a 32 KB stage).  The query producers only issue the requests.
 constexpr int kBRing = 3;
+// Both at once (kDma and kBDma, FlatFilterArgs::bdma == 2): the same nine 16 KB units of LDS dealt differently -- three row stages
+// and three B stages instead of five and two (5 + 3 would not fit 160 KB).  While the consumers read stage S, the rows and the B
+// operands of S+1 have landed and those of S+2 are in flight.
+constexpr int kDmaRingB = 3;
+static_assert(kDmaRingB * kDmaStageBytes + kBRing * kWsBStage * 16 <= kDmaRing * kDmaStageBytes + 2 * kWsBStage * 16, "no more LDS than the 5 + 2 kernel");
 // The gate of the 16x16x32 consumers.  Register reg of row subtile rs (16 rows) is row rs*16 + 4*kg + reg of the tile, column
 // c of the wave's query sixteenth qs: a lane owns FOUR query columns, wave*64 + 16 qs + c, and 32 rows of each.  The same
 // structure as filter_gate: one max per column, one vote for the wave, then one per 128 x 16 block; bit rs*4 + reg of a
@@ -906,7 +912,9 @@ __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
   static_assert(!kM16 || ((kDma || kBDma) && !kL2 && !kSample && !kTiming && kAbl == 0), "16x16x32: final pass, inner-product space, no experiment variants");
   static_assert(!kM16 || kDma || !kBf16, "16x16x32 with the rows through registers: f32 rows");
   constexpr int kAStride = kM16 ? kFAStride16 : kFAStride;
-  static_assert(!kBDma || (!kDma && !kTiming && !kSample && kAbl == 0), "B by DMA: rows through registers, final pass, no experiment variants");
+  static_assert(!kBDma || (!kTiming && !kSample && kAbl == 0), "B by DMA: final pass, no experiment variants");
+  static_assert(!kBDma || !kDma || !kL2, "L2 on the DMA row path: the half norms ride with a B register set");
+  constexpr int kRowRing = kBDma ? kDmaRingB : kDmaRing;                    // stages of the DMA row ring
   static_assert(!kDma || (kBf16 && !kSample && !kTiming), "the DMA row path serves a 16-bit row stream in the final pass");
   static_assert(!kDma || !kL2 || (!kBfMma && kAbl == 0), "L2 on the DMA row path: the f16 image of f32 rows, no experiment variants");
   // (experiment kernels only, kAbl != 0: a.ablate switches pieces of the pipeline OFF -- results invalid, times tell what bounds a stage:
@@ -915,7 +923,7 @@ __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
   const uint32_t abl = kAbl != 0 ? exp_ablate(a) : 0u;
   extern __shared__ _Float16 lds_a[];
   constexpr uint32_t kBufHalfs = kFTileRows * kAStride;                     // one A stage
-  uint4 *lds_b = reinterpret_cast<uint4 *>(lds_a + (kDma ? kDmaRing * kDmaStageBytes / 2 : 2 * kBufHalfs));   // [2][kWsBStage]
+  uint4 *lds_b = reinterpret_cast<uint4 *>(lds_a + (kDma ? kRowRing * kDmaStageBytes / 2 : 2 * kBufHalfs));   // [2][kWsBStage] (kBDma: [kBRing])
   uint32_t *lds_ring = reinterpret_cast<uint32_t *>(lds_b + (kBDma ? kBRing : 2) * kWsBStage); // [4 consumer waves][3][64]
   uint32_t *hn_lds = lds_ring + 4 * kRingWords;                              // [2][128] (kL2)
   // [2]: cancellation seen during tile T -> word T & 1.  (An LDS-qualified pointer: through a generic one the accesses
@@ -948,7 +956,7 @@ __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
   if (tid < 2) lds_stop[tid] = 0;
   if constexpr (kAbl != 0) {
     if (abl != 0) {   // (stages that are never written must not hold NaNs: every pair would pass the gate)
-      constexpr uint32_t a_bytes = kDma ? kDmaRing * kDmaStageBytes : 2 * kBufHalfs * 2;
+      constexpr uint32_t a_bytes = kDma ? kRowRing * kDmaStageBytes : 2 * kBufHalfs * 2;
       for (uint32_t i = tid; i < (a_bytes + 2 * kWsBStage * 16) / 16; i += kWsThreads) reinterpret_cast<uint4 *>(lds_a)[i] = make_uint4(0, 0, 0, 0);
     }
   }
@@ -995,7 +1003,7 @@ __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
     else if (pr == 2) __builtin_amdgcn_s_setprio(2);
     else if (pr == 3) __builtin_amdgcn_s_setprio(3);
   }
-  if constexpr (kBDma) {
+  if constexpr (kBDma && !kDma) {
     if (wave >= 6) {
       // ================================ query producer, LDS-DMA ========================================
       // wave p: query tiles 4p .. 4p+3, sixteen 1 KB pieces per stage.  Iteration S: request B(S+2) into the ring slot
@@ -1103,10 +1111,69 @@ __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
       const uint32_t voff_e = rpart + (((lane & 7u) ^ (lane >> 4)) * 16u), voff_o = rpart + (((lane & 7u) ^ (4u + (lane >> 4))) * 16u);
       const uint32_t step = 8u * a.row_stride_f * 2u;
       __attribute__((address_space(3))) char *ring0 = (__attribute__((address_space(3))) char *)lds_a;
-      const uint32_t b_lds = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)lds_b) + (pw * 8u * kWave + lane) * 16u;
       const uint32_t ks_n = a.row_stride_f / 16;
       FPos ld{first_tile * row_step, 0, total, row_step}, lb = ld;
       uint32_t slot_i = 0;                                                   // ring slot of the next row request (bytes)
+#define VK_WS_DMA_ROWS()                                                                                            \
+      {                                                                                                             \
+        const __amdgpu_buffer_rsrc_t r_ =                                                                           \
+            ws_rsrc(static_cast<const char *>(dma_rows) + ((size_t)ld.row0 * a.row_stride_f + (size_t)ld.st * kFStageK) * 2u); \
+        _Pragma("unroll") for (int u = 0; u < 4; ++u)                                                               \
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(r_, (__attribute__((address_space(3))) void *)(ring0 + slot_i + (pw * 4u + u) * 1024u), 16, \
+                                                   (int)((u & 1) ? voff_o : voff_e), (int)(u * step), 0, 2);         \
+        fpos_advance(ld, stages);                                                                                   \
+        slot_i = slot_i + kDmaStageBytes == kRowRing * kDmaStageBytes ? 0u : slot_i + kDmaStageBytes;               \
+      }
+      if constexpr (kBDma) {
+        // B by DMA too (kBDma): the wave's share of a B stage is eight 1 KB pieces of the fragment-major query copy -- query tiles
+        // 2 pw, 2 pw + 1, K-steps 0 .. 3 -- requested straight into the B ring, where they land as the consumers read them: no
+        // register sets, no LDS stores.  Rings of kDmaRingB row stages and kBRing B stages.  The requests leave in the order
+        // B(0) rows(0) B(1) rows(1) | B(2) rows(2) | B(3) rows(3) ... (a bar: an iteration; sched_barrier pins the order) and
+        // return in it.  Iteration S requests B(S+2) and rows(S+2) into the slots stage S-1 left, then waits for B(S+1) and
+        // rows(S+1): what stays in flight is what this iteration asked for, 8 + 4 = 12 requests -- nothing is waited for
+        // earlier than it is needed.
+        static_assert(kDmaRingB == 3 && kBRing == 3, "the request order and the wait count below are those of 3 + 3");
+        constexpr int kInFlight = 12;
+        __attribute__((address_space(3))) char *bring = (__attribute__((address_space(3))) char *)lds_b;
+        uint32_t slot_b = 0;                                                 // ring slot of the next B request (bytes)
+#define VK_WS_DMA_BREQ()                                                                                            \
+        {                                                                                                           \
+          _Pragma("unroll") for (int t2 = 0; t2 < 2; ++t2) {                                                        \
+            const uint32_t jt0 = pw * 2 + t2, jt = jt0 < a.nqt ? jt0 : a.nqt - 1;                                   \
+            const __amdgpu_buffer_rsrc_t r_ = ws_rsrc(reinterpret_cast<const char *>(a.q16) + ((size_t)jt * ks_n + lb.st * 4) * kWave * 16); \
+            _Pragma("unroll") for (int kk = 0; kk < 4; ++kk)                                                        \
+              __builtin_amdgcn_raw_ptr_buffer_load_lds(r_, (__attribute__((address_space(3))) void *)(bring + slot_b + ((pw * 2u + t2) * 4u + kk) * 1024u), \
+                                                       16, (int)(lane * 16), (int)(kk * 1024), 0, 0);               \
+          }                                                                                                         \
+          fpos_advance(lb, stages);                                                                                 \
+          slot_b = slot_b + kWsBStage * 16u == kBRing * kWsBStage * 16u ? 0u : slot_b + kWsBStage * 16u;            \
+          __builtin_amdgcn_sched_barrier(0);                                                                        \
+        }
+        VK_WS_DMA_BREQ()
+        VK_WS_DMA_ROWS()
+        __builtin_amdgcn_sched_barrier(0);
+        VK_WS_DMA_BREQ()
+        VK_WS_DMA_ROWS()
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kInFlight) : "memory");
+        VK_WS_PBARRIER()
+        while (left_c != 0 && !stop) {
+          if (st_c == 0 && lane == 0 && pw == 0 && a.cancel && (tile_c % kCancelPollTiles) == 0) {
+            if (__hip_atomic_load(a.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0) lds_stop[tile_c & 1] = 1;
+          }
+          VK_WS_DMA_BREQ()
+          VK_WS_DMA_ROWS()
+          __builtin_amdgcn_sched_barrier(0);
+          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kInFlight) : "memory");
+          left_c -= 1;
+          st_c += 1;
+          if (st_c == stages) VK_WS_TILE_END(VK_WS_PBARRIER()) else VK_WS_PBARRIER();
+        }
+#undef VK_WS_DMA_BREQ
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // (nothing may land in LDS after the block has gone)
+        return;
+      }
+      const uint32_t b_lds = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)lds_b) + (pw * 8u * kWave + lane) * 16u;
       // kL2: the tile's half norms (hn16) travel WITH the B operands -- one more load per B set, one more LDS store per stage,
       // so every producer wave keeps one request count and the waits below stay constants.  Wave pw: the words of rows 32 pw ..
       // 32 pw + 31 of the tile stage S+3 belongs to (both halves of the wave ask for the same 32 words; rows beyond n_rows clamp
@@ -1117,16 +1184,6 @@ __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
       constexpr int kInFlight = kL2 ? 30 : 28;                               // requests behind B(S+1) and the rows of S+1 (below)
       const uint32_t hn_row = 32u * pw + (lane & 31u);
       const uint32_t hn_lds_at = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)hn_lds) + hn_row * 4u;
-#define VK_WS_DMA_ROWS()                                                                                            \
-      {                                                                                                             \
-        const __amdgpu_buffer_rsrc_t r_ =                                                                           \
-            ws_rsrc(static_cast<const char *>(dma_rows) + ((size_t)ld.row0 * a.row_stride_f + (size_t)ld.st * kFStageK) * 2u); \
-        _Pragma("unroll") for (int u = 0; u < 4; ++u)                                                               \
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(r_, (__attribute__((address_space(3))) void *)(ring0 + slot_i + (pw * 4u + u) * 1024u), 16, \
-                                                   (int)((u & 1) ? voff_o : voff_e), (int)(u * step), 0, 2);         \
-        fpos_advance(ld, stages);                                                                                   \
-        slot_i = slot_i + kDmaStageBytes == kDmaRing * kDmaStageBytes ? 0u : slot_i + kDmaStageBytes;               \
-      }
 #define VK_WS_DMA_BLOAD(B)                                                                                          \
       {                                                                                                             \
         _Pragma("unroll") for (int t2 = 0; t2 < 2; ++t2) {                                                          \
@@ -1476,7 +1533,7 @@ __device__ __forceinline__ void flat_filter_body(const FlatFilterArgs &a) {
     left_c -= 1;
     st_c += 1;
     par ^= 1;
-    if constexpr (kDma) dma_slot = dma_slot + kDmaStageBytes == kDmaRing * kDmaStageBytes ? 0u : dma_slot + kDmaStageBytes;
+    if constexpr (kDma) dma_slot = dma_slot + kDmaStageBytes == kRowRing * kDmaStageBytes ? 0u : dma_slot + kDmaStageBytes;
     if constexpr (kBDma) b_slot = b_slot + kWsBStage == kBRing * kWsBStage ? 0u : b_slot + kWsBStage;
     if (st_c == stages) {
       if (has_q) {
@@ -1560,6 +1617,24 @@ __global__ __launch_bounds__(kWsThreads, 1) void flat_filter_early_kernel(FlatFi
 __global__ __launch_bounds__(kWsThreads, 1) void flat_filter_early_bfmma_dma_kernel(FlatFilterArgs a) {
   flat_filter_body<true, false, false, false, 0, true, true>(a);
 }
+// Rows AND B operands by DMA (FlatFilterArgs::bdma == 2, inner-product space): the final and the early pass over bf16 rows or
+// a bf16 image, and over the f16 image of f32 rows, with either matrix-core shape
+template <bool kM16>
+__global__ __launch_bounds__(kWsThreads, 1) void flat_filter_bfmma_dma_bdma_kernel(FlatFilterArgs a) {
+  flat_filter_body<true, false, false, false, 0, true, true, true, kM16>(a);
+}
+template <bool kM16>
+__global__ __launch_bounds__(kWsThreads, 1) void flat_filter_early_bfmma_dma_bdma_kernel(FlatFilterArgs a) {
+  flat_filter_body<true, false, false, false, 0, true, true, true, kM16>(a);
+}
+template <bool kM16>
+__global__ __launch_bounds__(kWsThreads, 1) void flat_filter_image_dma_bdma_kernel(FlatFilterArgs a) {
+  flat_filter_body<true, false, false, false, 0, false, true, true, kM16>(a);
+}
+template <bool kM16>
+__global__ __launch_bounds__(kWsThreads, 1) void flat_filter_early_image_dma_bdma_kernel(FlatFilterArgs a) {
+  flat_filter_body<true, false, false, false, 0, false, true, true, kM16>(a);
+}
 #ifdef VK_EXPERIMENTS
 template <int kAbl>   // (experiments, VK_FILTER_ABLATE)
 __global__ __launch_bounds__(kWsThreads, 1) void flat_filter_bfmma_dma_abl_kernel(FlatFilterArgs a) {
@@ -1577,8 +1652,9 @@ __global__ __launch_bounds__(kWsThreads, 1) void flat_filter_sample_kernel(FlatF
   flat_filter_body<kBf16, kL2, false, true>(a);
 }
 
-size_t flat_filter_dma_lds_bytes() {
-  return (size_t)kDmaRing * kDmaStageBytes + (size_t)2 * kWsBStage * 16 + (size_t)4 * kRingWords * 4 + (size_t)2 * kFTileRows * 4 + 16;
+size_t flat_filter_dma_lds_bytes(bool bdma = false) {   // (bdma: B by DMA as well -- 3 + 3 stages instead of 5 + 2, the same bytes)
+  return (size_t)(bdma ? kDmaRingB : kDmaRing) * kDmaStageBytes + (size_t)(bdma ? kBRing : 2) * kWsBStage * 16 + (size_t)4 * kRingWords * 4 +
+         (size_t)2 * kFTileRows * 4 + 16;
 }
 size_t flat_filter_bdma_lds_bytes(bool m16) {
   return (size_t)2 * kFTileRows * (m16 ? kFAStride16 : kFAStride) * sizeof(_Float16) + (size_t)kBRing * kWsBStage * 16 + (size_t)4 * kRingWords * 4 +
@@ -1669,6 +1745,21 @@ hipError_t launch_flat_filter(const FlatFilterArgs &a, uint32_t blocks, hipStrea
                    : reinterpret_cast<const void *>(&flat_filter_bdma_kernel<false, false, false, false, true>);
       lds = flat_filter_bdma_lds_bytes(true);
     }
+  }
+  // B by DMA on the DMA row path as well (option filter-bdma = 2): the passes of the inner-product space that stream 16-bit rows
+  // by DMA -- bf16 rows or a bf16 image, the f16 image of f32 rows -- with either shape; L2 keeps the B register sets
+  if (a.bdma == 2 && a.mode == 0 && !exp_variant && !a.l2 && ((a.qbf16 && a.dma) || a.rows16 != nullptr)) {
+    if (a.qbf16 && a.dma)
+      fn = a.mfma16 ? (a.early ? reinterpret_cast<const void *>(&flat_filter_early_bfmma_dma_bdma_kernel<true>)
+                               : reinterpret_cast<const void *>(&flat_filter_bfmma_dma_bdma_kernel<true>))
+                    : (a.early ? reinterpret_cast<const void *>(&flat_filter_early_bfmma_dma_bdma_kernel<false>)
+                               : reinterpret_cast<const void *>(&flat_filter_bfmma_dma_bdma_kernel<false>));
+    else
+      fn = a.mfma16 ? (a.early ? reinterpret_cast<const void *>(&flat_filter_early_image_dma_bdma_kernel<true>)
+                               : reinterpret_cast<const void *>(&flat_filter_image_dma_bdma_kernel<true>))
+                    : (a.early ? reinterpret_cast<const void *>(&flat_filter_early_image_dma_bdma_kernel<false>)
+                               : reinterpret_cast<const void *>(&flat_filter_image_dma_bdma_kernel<false>));
+    lds = flat_filter_dma_lds_bytes(true);
   }
 #ifdef VK_EXPERIMENTS
   if (a.timing) {

@@ -182,7 +182,8 @@ struct FlatFilterArgs {
   const float *queries;       // [nq][q_stride_f] f32, padded (input of flat_qprep_kernel)
   uint32_t q_stride_f;
   uint32_t qbf16;             // bf16 rows, inner-product space: q16 holds bf16 fragments and the bf16 matrix-core instruction multiplies
-  uint32_t bdma;              // final pass: the B operands go L2 -> LDS by DMA, a ring of three stages (VK_FILTER_BDMA=0: through registers)
+  uint32_t bdma;              // final pass: the B operands go L2 -> LDS by DMA, a ring of three stages (VK_FILTER_BDMA=0: through registers;
+                              // 1: where the rows go through registers; 2: on the DMA row path as well, inner-product space)
   uint32_t dma;               // with qbf16, final pass: the rows go HBM -> LDS by DMA (VK_FILTER_DMA=0: through registers)
   void *q16;                  // [nqt][row_stride_f/16][64][8] f16 (qbf16: bf16): the queries in MFMA fragment order (written by qprep)
   // per query column (written by qprep): the error margin of an approximate score against a row of norm R as a

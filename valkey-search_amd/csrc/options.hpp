@@ -92,7 +92,7 @@ inline const OptDesc &opt_desc(uint32_t id) {
       {"filter-prepass-rows", "VK_FILTER_PREPASS", 262144, 1024, kMax},
       {"filter-cap", "VK_FILTER_CAP", 8192, 64, 1u << 24},
       {"filter-spill-chunks", "VK_FILTER_SPILL_CHUNKS", 1024, 0, 1u << 20},
-      {"filter-bdma", "VK_FILTER_BDMA", 1, 0, 1},
+      {"filter-bdma", "VK_FILTER_BDMA", 2, 0, 2},                                // B operands by LDS DMA: 1 where rows go through registers, 2 on the DMA row path too (rings of 3 + 3)
       {"filter-row-dma", "VK_FILTER_DMA", 1, 0, 1},
       {"filter-bf16-mfma", "VK_FILTER_BF16_MFMA", 1, 0, 1},
       {"flat-force-scan", "VK_FLAT_FORCE_SCAN", 0, 0, 1},
